@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — rays/s of the ProNeRF inference hot path (render_rays) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's frame if --dump-outputs is given and prints the line: the
+headline (`value`, `ms_per_step`) with `frame_sha256` and `outputs_finite`, nothing else.  Every block described below beyond that
+(`per_rank`, `roofline` / `kernels`, the baselines, `steady_state`, `shard_rehearsal`, `chunked_1024`, `variants`, `weights_*`, `train`)
+runs only with --full; the --no-* options switch single blocks of a --full run off.  --dump-outputs DIR writes DIR/rgbd.npy: the
+[762048, 4] float32 rgb+depth frame (pixel order) that the last timed step computed, as render_rays returns it; the inputs are seeded,
+so two builds can be compared output for output.
 
 Workload (BASELINE.json configs[1]): one 1008x756 LLFF-Fern-geometry frame =
 762 048 rays, 8 samples/ray, 4 neighbour views, 48 ray-encoding points; synthetic poses/images
@@ -20,15 +27,15 @@ in HBM before the timed region, exactly like the reference's timed loop
 ("strong" scaling: the frame is fixed).
 
 Rank 0 prints ONE JSON line (see the driver contract).  Every line carries `frame_sha256` — the assembled frame of the last timed step: the same
-digest at every N — and, at N > 1, `per_rank` (device, rays, render ms alone, gather ms alone: measured behind the timed region, so that a scaling
-line explains itself).  At N=1 it carries `roofline`, `cpu_baseline`
+digest at every N — and, at N > 1 with --full, `per_rank` (device, rays, render ms alone, gather ms alone: measured behind the timed region, so that a scaling
+line explains itself).  At N=1 with --full it carries `roofline`, `cpu_baseline`
 (the CPU oracle on the host cores, 65 536 rays of the same frame) and `gpu_eager_baseline`: the oracle's
 eager fp32 torch graph on the same GPU, whole frame in one call, device events — BASELINE.md §4 item 2,
 "the reference single-GPU PyTorch rays/s" that BASELINE.json's >= 10x target is measured against.  No
 published number exists for the metric, so `vs_baseline` is value / that measured baseline
 and `vs_baseline_kind` says so.  Both baselines run after the timed region; oracle/ is imported only there.
 
-Also after the timed region, at N=1 (each can be switched off): `steady_state` — the timed loop again over >= 2 s of frames, with socket power /
+Also after the timed region, at N=1 with --full (each can be switched off): `steady_state` — the timed loop again over >= 2 s of frames, with socket power /
 package cap / shader clock polled from rocm-smi meanwhile (the path is power-limited: DESIGN.md 4.4); `shard_rehearsal` — this GPU's time on the
 first / middle / last rank's share of the frame at N = 2, 4, 8 (contiguous and block-cyclic) and on 1024- / 4096-ray calls; `chunked_1024` — the
 same frame as 745 calls of <= 1024 rays (the literal reading of configs[1]): on one stream, over four streams, and each as one hipGraph, next to
@@ -69,6 +76,9 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10, help='the chip needs ~5 frames from idle to its steady clock')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's frame to DIR/rgbd.npy ([n, 4] float32 rgb+depth, pixel order; rank 0)")
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run every extra block (per-rank figures at N > 1; roofline, '
+                    'baselines, steady state, rehearsals, variants, trained nets, training at N = 1); without it the run prints the headline only')
     ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU oracle timing (rank 0, N=1)')
     ap.add_argument('--cpu-sample-rays', type=int, default=65536, help='SURVEY.md §8(d): >= 65 536 rays')
     ap.add_argument('--no-gpu-eager-baseline', action='store_true', help='skip the eager-PyTorch-on-GPU baseline (rank 0, N=1)')
@@ -87,7 +97,10 @@ def parse():
                          "second-pass rays) or contiguous ranges (SURVEY.md 8(e); the slowest shard then sets the frame rate)")
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N>1 ('nccl' = RCCL; 'gloo' to rehearse "
                     'the multi-rank path with several ranks sharing one GPU)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def host_cores():
@@ -701,14 +714,15 @@ def main():
     # per-kernel durations over the timed region itself: the library records a HIP event before / after each of the three
     # kernels of a frame on the launch stream (pnrf_ctx_profile_begin), four event records per frame, read after the region
     PROF_FRAMES = 256
-    if world == 1:
+    profiled = world == 1 and args.full              # the events feed `roofline` / `kernels` only
+    if profiled:
         rend.ctx.profile_begin(min(args.steps, PROF_FRAMES))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
-    prof, prof_frames = rend.ctx.profile_end() if world == 1 else (None, 0)
+    prof, prof_frames = rend.ctx.profile_end() if profiled else (None, 0)
     dbg(f'timed region done: {dt:.3f}s')
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -718,9 +732,14 @@ def main():
     # the assembled frame of the last timed step, as bytes: the same digest at every N (ray shards + gather change no row) — tests/test_dist_gpu.py,
     # tests/test_bench_gpu.py compare it with the N = 1 line's
     import hashlib
-    frame_sha = hashlib.sha256(fg.frame(last_buf[0]).contiguous().cpu().numpy().tobytes()).hexdigest() if rank == 0 else None
+    frame = fg.frame(last_buf[0]).contiguous().cpu().numpy() if rank == 0 else None
+    frame_sha = hashlib.sha256(frame.tobytes()).hexdigest() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'rgbd.npy'), frame.astype(np.float32, copy=False))
+    del frame
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # after the timed region: where a frame's time goes on every rank — its render alone (device events) and the exchange alone (all-gather +
         # reorder of an already rendered tile, host clock around fence) — so that a SCALE line explains itself
         reps = 10
@@ -762,9 +781,9 @@ def main():
             'launcher': ('self (bench.py started its own ranks)' if os.environ.get('PNRF_BENCH_CHILD') else
                          'torch.distributed.run' if world > 1 else None),
             'config': {'workload': 'LLFF fern geometry 1008x756 frame (762048 rays), 8 samples/ray, 4 neighbour views, 48 ray-encoding points, '
-                                   'bf16 NeRF MLP, fp16 refine MLP (all-fp16 and all-bf16 timed beside it: variants); one pnrf_render_rays_fwd call renders the whole frame, as the reference does (the 1024-ray chunks of '
+                                   'bf16 NeRF MLP, fp16 refine MLP (all-fp16 and all-bf16 timed beside it with --full: variants); one pnrf_render_rays_fwd call renders the whole frame, as the reference does (the 1024-ray chunks of '
                                    'configs[1] = 4 of the 256-column workgroup batches each persistent kernel walks inside its single launch; '
-                                   'the frame as 745 separate 1024-ray calls is timed beside it: chunked_1024)',
+                                   'the frame as 745 separate 1024-ray calls is timed beside it with --full: chunked_1024)',
                        'rays_per_step': n_total, 'rays_per_gpu': counts[0], 'rays_per_rank': counts,
                        'gather_bytes_per_rank_per_frame': (fg.cmax * 4 * 4 if world > 1 else 0),
                        'gather_bytes_per_frame': (fg.cmax * 4 * 4 * world if world > 1 else 0),
@@ -775,8 +794,9 @@ def main():
             'per_rank': per_rank,
             'algorithmic_flop_per_ray': FLOP_PER_RAY,
             'e2e_mfma_tflops': value * FLOP_PER_RAY / 1e12,
+            'full': bool(args.full),
         }
-        if world == 1:
+        if world == 1 and args.full:
             flops = {'sampler_kernel': 2 * MAC_SAMPLER, 'refine_kernel': 2 * MAC_REFINE, 'nerf_kernel': 2 * MAC_NERF}
             # the sampler's algorithmic FLOPs are priced against the peak of the MFMA dtype it runs on (f16 = bf16 rate)
             peaks = {'sampler_kernel': PEAK_F32 if sampler_f32 else PEAK_BF16, 'refine_kernel': PEAK_BF16, 'nerf_kernel': PEAK_BF16}

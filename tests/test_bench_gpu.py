@@ -1,11 +1,13 @@
-"""GPU: bench.py's JSON contract, on small step counts — the N = 1 line with `roofline`, `cpu_baseline` and `gpu_eager_baseline`, and the
-N = 2 path (two ranks sharing the one GPU of the box, `gloo` instead of RCCL) so that the multi-rank code cannot rot between the
-driver's multi-GPU runs.  bench.py runs as a fresh child process, as the driver starts it."""
+"""GPU: bench.py's JSON contract, on small step counts — the plain N = 1 line with its output dump, the --full N = 1 line with `roofline`,
+`cpu_baseline` and `gpu_eager_baseline`, and the N = 2 path (two ranks sharing the one GPU of the box, `gloo` instead of RCCL) so that the
+multi-rank code cannot rot between the driver's multi-GPU runs.  bench.py runs as a fresh child process, as the driver starts it."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,13 +21,13 @@ def _last_json(out):
     return json.loads(lines[-1])
 
 
-QUICK = ['--no-cpu-baseline', '--no-gpu-eager-baseline', '--no-sustained', '--no-chunked', '--no-variants', '--no-shard-rehearsal', '--steady-seconds', '0',
+QUICK = ['--full', '--no-cpu-baseline', '--no-gpu-eager-baseline', '--no-sustained', '--no-chunked', '--no-variants', '--no-shard-rehearsal', '--steady-seconds', '0',
          '--no-train', '--no-optimizer-weights']
 _N1 = {}
 
 
 def n1_frame_digest():
-    """sha256 of the frame the N = 1 bench renders (bench.py --gpus 1, every extra block off): what every N > 1 line's assembled frame must hash to."""
+    """sha256 of the frame the N = 1 bench renders (bench.py --gpus 1 --full, every extra block off): what every N > 1 line's assembled frame must hash to."""
     if 'sha' not in _N1:
         env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
         r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1'] + QUICK, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -42,7 +44,7 @@ def check_per_rank(j, n):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '5', '--warmup', '3', '--cpu-sample-rays', '8192', '--eager-reps', '2'], cwd=ROOT,
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--steps', '5', '--warmup', '3', '--cpu-sample-rays', '8192', '--eager-reps', '2'], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -62,10 +64,28 @@ def test_bench_single_gpu_line():
     assert len(j['frame_sha256']) == 64 and j['per_rank'] is None
 
 
+def test_bench_plain_line_dumps_the_last_frame(tmp_path):
+    """The plain line (no --full): the headline and no block measured beside it; --dump-outputs writes the frame of the last timed step, the
+    bytes `frame_sha256` hashes, which equal the --full run's frame."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '4', '--warmup', '2', '--dump-outputs', str(tmp_path / 'out')], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _last_json(r.stdout)
+    assert j['n_gpus'] == 1 and j['steps'] == 4 and j['warmup'] == 2 and j['full'] is False and j['unit'] == 'rays/s' and j['higher_is_better'] is True
+    assert j['outputs_finite'] and abs(j['value'] - 762048 / (j['ms_per_step'] * 1e-3)) < 1e-3 * j['value'] and j['per_rank'] is None
+    extra = {'roofline', 'kernels', 'sampler_two_pass', 'steady_state', 'shard_rehearsal', 'chunked_1024', 'variants', 'gpu_eager_baseline', 'weights_optimizer',
+             'weights_scene3d', 'train', 'cpu_baseline'}
+    assert not extra & set(j), extra & set(j)
+    a = np.load(tmp_path / 'out' / 'rgbd.npy')
+    assert a.dtype == np.float32 and a.shape == (762048, 4) and np.isfinite(a).all()
+    assert hashlib.sha256(a.tobytes()).hexdigest() == j['frame_sha256'] == n1_frame_digest()
+
+
 def test_bench_two_ranks_on_one_gpu_gloo():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', '29517',
-           'bench.py', '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--no-cpu-baseline']
+           'bench.py', '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -80,7 +100,7 @@ def test_bench_two_ranks_without_a_launcher():
     """`python3 bench.py --gpus 2` as the driver starts the N = 1 bench (no torch.distributed.run): bench.py starts its own ranks before
     anything touches the GPU and relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--partition', 'contiguous']
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--partition', 'contiguous', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)

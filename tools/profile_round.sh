@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"      # a second run into the same tag must not leave the first one's CSVs beside its own
 export TMPDIR=/tmp
 python3 -c "from pronerf_amd import build; print(build._digest('inference'))" > "$OUT/csrc_digest.txt"      # what bench.py checks before quoting this profile
-python3 bench.py --steps 20 --warmup 10 --no-train > "$OUT/bench.json"
+python3 bench.py --full --steps 20 --warmup 10 --no-train > "$OUT/bench.json"
 python3 -c "import json,sys; j=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1]); json.dump(j['shard_rehearsal'], open('$OUT/shard_rehearsal.json','w'), indent=1)"
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-gpu-eager-baseline --no-sustained --no-chunked --no-variants --no-train --no-shard-rehearsal --no-optimizer-weights --steady-seconds 0 > "$OUT/bench_under_rocprof.json"
