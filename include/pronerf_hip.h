@@ -430,6 +430,15 @@ int pnrf_train_stage2_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_batch_t* batch
  * loss = img2mse(rgb_map1); gradients for the 12 NeRF layers only. */
 int pnrf_train_explore_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_batch_t* batch, int n_mult, int dir1, float* loss,
                                float* rgb_map1, void* stream);
+/* y = net(x); y.backward(dy) for ONE of the trainer's three nets, through the dispatch of the iterations (preparation launch, product kind,
+ * weight-gradient tile choice, engine / chain / per-layer path chosen by row count, grouped weight-gradient launch).  Overwrites that net's
+ * layer gradients only (kind 1 of pnrf_trainer_read).  Test-facing: the output gradient is the caller's, not the losses'.
+ * net 0 sampler: x dev [n,288], dy / y dev [n,27];  net 1 refine: x dev [n,144], dy / y dev [n,35]  (S, rays unused: 0 / NULL; d_pts NULL);
+ * net 2 fine net (NeRF class): x = pts dev [n*S,3], rays dev [n,11] (view directions at 8:11, repeated S times), 1 <= S <= max_samples,
+ *       dy = d raw dev [n*S,4], y = raw dev [n*S,4], d_pts dev [n*S,3] (n*S <= 8 max_rays) or NULL (the exploration's branch without
+ *       position gradient).  n in [1, max_rays] for every net. */
+int pnrf_trainer_net_fwd_bwd(pnrf_trainer_t* t, int net, const float* x, const float* rays, int64_t n, int S, const float* dy,
+                             float* y, float* d_pts, void* stream);
 /* Both iteration entry points copy the batch into buffers of the trainer with one launch; with pnrf_trainer_set_graph(t, 1) they then replay
  * their ~100-kernel launch sequence as a hipGraph (captured from the given stream — the legacy default stream is served through a stream of
  * the trainer's own — the first time a configuration (ray count, views, flags, stream) is seen; up to 8 configurations are kept).  Default

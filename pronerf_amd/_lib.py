@@ -89,6 +89,7 @@ SIGNATURES = {
     'pnrf_train_stage2_fwd_bwd': (_i, [_p, _p, _p, _p, _p]),
     'pnrf_train_explore_fwd_bwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),
     'pnrf_trainer_adam_step': (_i, [_p, _i, _f, _f, _f, _f, _f, _p]),
+    'pnrf_trainer_net_fwd_bwd': (_i, [_p, _i, _p, _p, _i64, _i, _p, _p, _p, _p]),
 }
 
 

@@ -2079,6 +2079,43 @@ int check_batch(const pnrf_trainer* t, const pnrf_train_batch_t* bt, const float
 
 }  // namespace
 
+// The start of an iteration as one launch (iter_prepare_kernel): whichever derived weight forms the coming pass reads are refreshed — the fp16
+// planes of the sampler / refine nets always; the fine net's planes unless both of its chains run on the engine over R sample rows; the chains'
+// fragment streams (and the column norms, cmax swapped) if the forward chain does — and the max-|gradient| slots are cleared.  bt != NULL: the
+// batch (n rays, S samples of jitter / noise per ray) is copied into the staging buffers by the same launch.  Shared by run_iteration and
+// pnrf_trainer_net_fwd_bwd, so that the operator-level entry point prepares exactly as the iterations do.
+static int prepare_iteration(pnrf_trainer* t, const pnrf_train_batch_t* bt, int64_t R, int S, hipStream_t s) {
+  const bool eng_f = engine_fwd(t, R), eng = engine_bwd(t, R);
+  static_assert(L_N + 12 == N_LAYERS && L_S < L_R && L_R < L_N, "the fine net's parameters are the tail of the flat parameter array (sp.total below)");
+  static_assert(TPB == 256, "tchain_norms_body: 16 columns x 16 partial sums per block");
+  PrepArgs pa = {};
+  if (t->planes_stale || (!eng && t->nerf_planes_stale)) {
+    pa.split = t->split;
+    if (eng) pa.split.total = t->L[L_N].w;                   // the parameters before the fine net's
+    pa.n_split = (unsigned)grid_for((int64_t)pa.split.total);
+    t->planes_stale = false;
+    if (!eng) t->nerf_planes_stale = false;
+  }
+  if (eng_f && t->streams_stale) {
+    pa.cmax_zero = t->tb_pack.cmax;                          // the array in use until now: cleared for the refresh after this one
+    t->tb_pack.cmax = t->cmax2 + (t->tb_pack.cmax == t->cmax2 ? 16 : 0);
+    pa.pack = t->tc_pack; pa.packb = t->tb_pack;
+    pa.n_pack = TC_NSLOTS * SLOT_FRAGS * 64 / TPB; pa.n_packb = TB_NSLOTS * SLOT_FRAGS * 64 / TPB; pa.n_norm = TB_NS * 16;
+    t->streams_stale = false;
+  }
+  if (bt) {
+    pa.stage = {bt->rays, bt->or_rays, bt->target, bt->jitter, bt->raw_noise, bt->ref_nos,
+                t->st_rays, t->st_or_rays, t->st_target, t->st_jitter, t->st_noise, t->st_ref_nos, bt->n, S, t->amax, N_AMAX * HG_SLOT};
+    pa.n_stage = (unsigned)grid_for(bt->n * 11);
+  } else {                                                     // no batch to stage: the stage blocks only clear the slots
+    pa.stage.amax = t->amax; pa.stage.n_amax = N_AMAX * HG_SLOT;
+    pa.n_stage = (unsigned)grid_for(N_AMAX * HG_SLOT);
+  }
+  hipLaunchKernelGGL(iter_prepare_kernel, dim3(pa.n_stage + pa.n_norm + pa.n_pack + pa.n_packb + pa.n_split), dim3(TPB), 0, s, pa);
+  PNRF_LAUNCH_CHECK();
+  return 0;
+}
+
 // Joint iteration: render_rays (training) + img2mse [+ a_mmrgb (img2mse(rgb_map0) + img2mse(mm_rgb))] + loss.backward() for all
 // three networks.  Stage 2 (refine2.py:525-680, 858-868): layout 0, eps 1e-5, clamp 0, jitter + sigma noise.  Stage-1 even
 // iterations (base.py:554-761 with train_sampler=True, :941-958): layout 1, eps 1e-6, clamp 10, no jitter / noise, a_mmrgb 1.
@@ -2154,34 +2191,7 @@ static int run_iteration(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, int ki
     PNRF_HIP(hipEventRecord(t->ev_in, caller));
     PNRF_HIP(hipStreamWaitEvent(s, t->ev_in, 0));
   }
-  {
-    // which of the derived weight forms this iteration reads: the fp16 planes of the sampler / refine nets always; the fine net's planes
-    // unless both of its chains run on the engine; the chains' fragment streams if the forward chain does.  One launch with the batch copy.
-    const int64_t R = N * S;
-    const bool eng_f = engine_fwd(t, R), eng = engine_bwd(t, R);
-    static_assert(L_N + 12 == N_LAYERS && L_S < L_R && L_R < L_N, "the fine net's parameters are the tail of the flat parameter array (sp.total below)");
-    static_assert(TPB == 256, "tchain_norms_body: 16 columns x 16 partial sums per block");
-    PrepArgs pa = {};
-    if (t->planes_stale || (!eng && t->nerf_planes_stale)) {
-      pa.split = t->split;
-      if (eng) pa.split.total = t->L[L_N].w;                   // the parameters before the fine net's
-      pa.n_split = (unsigned)grid_for((int64_t)pa.split.total);
-      t->planes_stale = false;
-      if (!eng) t->nerf_planes_stale = false;
-    }
-    if (eng_f && t->streams_stale) {
-      pa.cmax_zero = t->tb_pack.cmax;                          // the array in use until now: cleared for the refresh after this one
-      t->tb_pack.cmax = t->cmax2 + (t->tb_pack.cmax == t->cmax2 ? 16 : 0);
-      pa.pack = t->tc_pack; pa.packb = t->tb_pack;
-      pa.n_pack = TC_NSLOTS * SLOT_FRAGS * 64 / TPB; pa.n_packb = TB_NSLOTS * SLOT_FRAGS * 64 / TPB; pa.n_norm = TB_NS * 16;
-      t->streams_stale = false;
-    }
-    pa.stage = {bt->rays, bt->or_rays, bt->target, bt->jitter, bt->raw_noise, bt->ref_nos,
-                t->st_rays, t->st_or_rays, t->st_target, t->st_jitter, t->st_noise, t->st_ref_nos, N, S, t->amax, N_AMAX * HG_SLOT};
-    pa.n_stage = (unsigned)grid_for(N * 11);
-    hipLaunchKernelGGL(iter_prepare_kernel, dim3(pa.n_stage + pa.n_norm + pa.n_pack + pa.n_packb + pa.n_split), dim3(TPB), 0, s, pa);
-    PNRF_LAUNCH_CHECK();
-  }
+  T_RC(prepare_iteration(t, bt, N * S, S, s));
   pnrf_train_batch_t b = *bt;
   b.rays = t->st_rays; b.or_rays = t->st_or_rays; b.target = t->st_target; b.ref_nos = t->st_ref_nos;
   b.jitter = bt->jitter ? t->st_jitter : nullptr; b.raw_noise = bt->raw_noise ? t->st_noise : nullptr;
@@ -2240,6 +2250,55 @@ extern "C" int pnrf_train_explore_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_ba
   hipStream_t s = (hipStream_t)stream;
   return run_iteration(t, bt, 1, n_mult, dir1, S, loss, rgb_out, s,
                        [&](const pnrf_train_batch_t* b, hipStream_t st) { return explore_body(t, b, n_mult, dir1, st); });
+}
+
+// y = net(x); y.backward(dy) for one of the three nets through the iterations' own dispatch (prepare_iteration, product kind, engine / chain /
+// per-layer path by row count, grouped weight gradients): the net's inputs and output gradient go into the buffers the iterations use for them,
+// its layer gradients are overwritten, the other nets' are left alone.  A test-facing operator (include/pronerf_hip.h).
+extern "C" int pnrf_trainer_net_fwd_bwd(pnrf_trainer_t* t, int net, const float* x, const float* rays, int64_t n, int S, const float* dy, float* y,
+                                        float* d_pts, void* stream) {
+  PNRF_REQUIRE(t && x && dy && y, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: null pointer");
+  PNRF_REQUIRE(net >= 0 && net <= 2, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: net must be 0 (sampler), 1 (refine) or 2 (fine net), got %d", net);
+  PNRF_REQUIRE(n >= 1 && n <= t->max_rays, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: n = %lld outside [1, max_rays = %lld]", (long long)n,
+               (long long)t->max_rays);
+  hipStream_t s = (hipStream_t)stream;
+  if (net < 2) {
+    PNRF_REQUIRE(!d_pts, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: d_pts belongs to the fine net (net 2)");
+    const int first = net == 0 ? L_S : L_R, in0 = net == 0 ? 288 : 144, out = net == 0 ? 27 : 35;
+    float* x0 = net == 0 ? t->mm_input : t->refine_in;
+    float* const* h = net == 0 ? t->s_h : t->r_h;
+    float* yb = net == 0 ? t->s_y : t->r_y;
+    float* dyb = net == 0 ? t->d_sy : t->d_ry;
+    T_RC(prepare_iteration(t, nullptr, 0, 0, s));
+    PNRF_HIP(hipMemcpyAsync(x0, x, (size_t)n * in0 * 4, hipMemcpyDefault, s));
+    PNRF_HIP(hipMemcpyAsync(dyb, dy, (size_t)n * out * 4, hipMemcpyDefault, s));
+    begin_dw(t);
+    T_RC(elu_net_forward(t, first, x0, in0, h, n, s));
+    T_RC(layer_fwd(t, first + 6, h[5], 256, yb, out, n, T_ACT_NONE, s));
+    T_RC(elu_net_backward(t, first, dyb, out, h, x0, in0, n, s));
+    T_RC(flush_dw_reduce(t, s));
+    PNRF_HIP(hipMemcpyAsync(y, yb, (size_t)n * out * 4, hipMemcpyDefault, s));
+    return 0;
+  }
+  PNRF_REQUIRE(rays, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: the fine net needs rays [n, 11] (view directions at 8:11)");
+  PNRF_REQUIRE(S >= 1 && S <= t->max_samples, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: S = %d outside [1, max_samples = %d]", S, t->max_samples);
+  const int64_t R = n * S;
+  PNRF_REQUIRE(R <= t->max_rays * (int64_t)t->max_samples, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: n * S = %lld rows > max_rays * max_samples",
+               (long long)R);
+  // (the position gradient's buffer holds the 8 samples per ray of a stage-2 iteration: the exploration's larger S runs without it)
+  PNRF_REQUIRE(!d_pts || R <= 8 * t->max_rays, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: d_pts needs n * S <= 8 max_rays (got %lld rows)", (long long)R);
+  pnrf_train_batch_t b = {};
+  b.rays = rays; b.n = n;
+  T_RC(prepare_iteration(t, nullptr, R, S, s));
+  PNRF_HIP(hipMemcpyAsync(t->pts, x, (size_t)R * 3 * 4, hipMemcpyDefault, s));
+  PNRF_HIP(hipMemcpyAsync(t->d_raw, dy, (size_t)R * 4 * 4, hipMemcpyDefault, s));
+  begin_dw(t);
+  T_RC(nerf_forward(t, &b, S, s));
+  T_RC(nerf_backward(t, R, d_pts != nullptr, s));
+  T_RC(flush_dw_reduce(t, s));
+  PNRF_HIP(hipMemcpyAsync(y, t->raw, (size_t)R * 4 * 4, hipMemcpyDefault, s));
+  if (d_pts) PNRF_HIP(hipMemcpyAsync(d_pts, t->d_pts, (size_t)R * 3 * 4, hipMemcpyDefault, s));
+  return 0;
 }
 
 // How the layer products are computed.  0 (default): split-fp16 MFMA (pnrf_hgemm.h: fp32-grade, 22 significand bits per operand, fp32

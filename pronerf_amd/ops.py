@@ -632,6 +632,33 @@ class Trainer:
                   'pnrf_train_explore_fwd_bwd')
         return loss, rgb
 
+    _NETS = {'sampler': (0, 288, 27), 'refine': (1, 144, 35), 'nerf': (2, 3, 4)}
+
+    def net_fwd_bwd(self, net, x, dy, rays=None, S=1, want_dpts=False):
+        """y = net(x); y.backward(dy) for one of the three nets through the iterations' dispatch (pnrf_trainer_net_fwd_bwd); overwrites that net's
+        gradients only.  net 'sampler': x [n, 288], dy [n, 27]; 'refine': x [n, 144], dy [n, 35]; 'nerf': x = pts [n S, 3], rays [n, 11], dy = d raw
+        [n S, 4].  Returns (y, d_pts [n S, 3] or None)."""
+        if net not in self._NETS:
+            raise PnrfError(f'Trainer.net_fwd_bwd: net must be one of {sorted(self._NETS)}, got {net!r}')
+        k, fi, fo = self._NETS[net]
+        x = _chk(x, 'x', (fi,)).contiguous(); dy = _chk(dy, 'dy', (fo,)).contiguous()
+        rows = x.shape[0]
+        if tuple(dy.shape) != (rows, fo):
+            raise PnrfError(f'Trainer.net_fwd_bwd: dy must be [{rows}, {fo}], got {tuple(dy.shape)}')
+        if k == 2:
+            rays = _chk(rays, 'rays', (11,)).contiguous()
+            n = rays.shape[0]
+            if n * int(S) != rows:
+                raise PnrfError(f'Trainer.net_fwd_bwd: pts has {rows} rows, expected n * S = {n} * {S}')
+        else:
+            n, S, rays = rows, 0, None
+        y = torch.empty(rows, fo, device=x.device, dtype=f32)
+        d_pts = torch.empty(rows, 3, device=x.device, dtype=f32) if want_dpts else None
+        with torch.cuda.device(x.device):
+            check(_lib.load().pnrf_trainer_net_fwd_bwd(self.handle, k, _ptr(x), _ptr(rays), int(n), int(S), _ptr(dy), _ptr(y), _ptr(d_pts), _stream()),
+                  'pnrf_trainer_net_fwd_bwd')
+        return y, d_pts
+
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, nerf_only=False):
         """optimizer.step(); nerf_only: the stage-1 NeRF-only optimizer (own moments / step count) instead of the joint one."""
         with torch.cuda.device(self.device):

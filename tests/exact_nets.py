@@ -472,3 +472,332 @@ def mutate(w_list, layer, seed=0):
     r, c = np.argwhere(W != 0)[rs.randint(np.count_nonzero(W))]
     W[r, c] += 1
     return out, (layer, int(r), int(c))
+
+
+# ----------------------------------------------------------------------------------------------- training nets (pnrf_trainer_net_fwd_bwd)
+# What tests/test_exact_train_gpu.py runs (tests/test_exact_train_cpu.py certifies the same sets).  The trainer holds the three nets as plain
+# integer nets: its ELU is expm1f on the pre-activation (no log2(e) scale), so the refine net is refine_net's {'W', 'b'} as they are.
+TRAIN_LIVE = 1                         # the fine net's live coordinate (0 in every sample and view direction)
+TRAIN_MAX_RAYS, TRAIN_BIG = 12800, (1024, 256)          # the two trainers: (max_rays, max_samples 8) and (max_rays, max_samples)
+ELU_COUNTS = (1, 15, 16, 17, 4095, 4096, 4097, 8191, 8192, 8193, 12800)
+NERF_S8 = (1023, 1024, 1025, 1287, 4096, 4097, 8192, 8193)             # rays at S = 8: 8184 .. 65 544 rows
+NERF_BIG = ((64, 127), (64, 129), (64, 512), (256, 128), (256, 256), (256, 257))   # (S, rays) on the large trainer: 8128 .. 65 792 rows
+NERF_ONEHOT = (8, 4101)                # S, rays of the one-hot case: 32 808 rows (past 32 768)
+E_SIN = 2.0 ** -22                     # |sinf / cosf - sin / cos| of the embedding kernel (<= 2 ulp of a value <= 1), with a factor 2
+DY_NNZ = 384                           # nonzero rows of an output gradient over many rows: the weight-gradient sums stay below 2^24
+
+
+def nerf_cu_rays(cus):
+    """Rays at S = 8 whose 128-row batches outnumber the CUs, with a ragged last batch: 128 cus + 40 rows."""
+    return 16 * cus + 5
+
+
+def train_nets(live=TRAIN_LIVE):
+    """The trainer's 26 (W, b) in float64: sampler_net(), refine_net(4, 6) as plain integers, nerfcls_net(live) in pack order (pts0 .. 7,
+    feature, alpha, views, rgb)."""
+    s, r = sampler_net(), refine_net(4, synth.MMNETDEPTH)
+    Wn, bn = nerfcls_pack_order(nerfcls_net(live=live))
+    return list(s['W']) + list(r['W']) + Wn, list(s['b']) + list(r['b']) + bn
+
+
+def train_dy(rows, width, seed=0, nnz=DY_NNZ, big=(2049, -2051, 3001)):
+    """Integer output gradient [rows, width] (float32): every fifth row zero; of the others a quarter mix one large entry (``big``: more than
+    the 11 bits of the fp16 hi plane) with +-1 entries, the rest are small integers in [-3, 3].  nnz: only that many nonzero rows (spread over
+    the set, the first and the last row among them), so that the weight-gradient sums over many rows stay below 2^24."""
+    rs = np.random.RandomState(6007 + 31 * seed + width)
+    dy = rs.randint(-3, 4, (rows, width)).astype(np.float64)
+    mix = rs.rand(rows) < 0.25
+    dy[mix] = rs.choice((-1.0, 0.0, 1.0), (int(mix.sum()), width))
+    dy[mix, rs.randint(0, width, int(mix.sum()))] = rs.choice(big, int(mix.sum()))
+    dy[::5] = 0.0
+    if nnz is not None and nnz < rows:
+        keep = np.zeros(rows, bool)
+        keep[np.linspace(0, rows - 1, nnz).astype(np.int64)] = True
+        dy[~keep] = 0.0
+        dy[[0, rows - 1]] = rs.choice((-2.0, -1.0, 1.0, 2.0), (2, width))
+    return dy.astype(np.float32)
+
+
+def onehot_rows(rows):
+    """Rows of the one-hot output gradient: the first, the last, and those on each side of a 128-row and a 32 768-row boundary."""
+    cand = [0, rows - 1, 127, 128, 32767, 32768]
+    return sorted({r for r in cand if 0 <= r < rows})
+
+
+def hg_scale_for(mx):
+    """pnrf_hgemm.h hg_scale_for: the power of two s with s mx in [2^11, 2^12) (mx = 0 or non-finite: 1).  Elementwise."""
+    mx = np.asarray(mx, np.float64)
+    ok = (mx > 0) & np.isfinite(mx)
+    ex = np.frexp(np.where(ok, mx, 1.0))[1]
+    return np.where(ok, np.ldexp(1.0, np.clip(12 - ex, -100, 100)), 1.0)
+
+
+def split_exact(v, scale=1.0):
+    """Does every v * scale survive the kernels' split into fp16 hi + 2^-11 fp16 lo exactly?  (hi = fp16(x), lo = fp16((x - hi) 2^11).)"""
+    x = (np.asarray(v, np.float64) * scale).astype(np.float32)
+    if not np.array_equal(x.astype(np.float64), np.asarray(v, np.float64) * scale):
+        return False
+    with np.errstate(over='ignore', invalid='ignore'):
+        hi = x.astype(np.float16)
+        lo = ((x - hi.astype(np.float32)) * np.float32(2048)).astype(np.float16)
+        back = hi.astype(np.float64) + lo.astype(np.float64) / 2048
+    return bool(np.all(np.isfinite(back)) and np.array_equal(back, x.astype(np.float64)))
+
+
+def _assert_split(v, scale, what):
+    assert split_exact(v, scale), f'{what}: an operand does not survive the fp16 hi / lo split at scale {np.min(scale):.3g}'
+
+
+def _pow2_floor(x):
+    return np.ldexp(1.0, np.floor(np.log2(x)).astype(np.int64))
+
+
+def _split_hgemm(dz, what):
+    """A gradient operand of hgemm_kernel / dwh_*: one scale from the tensor's recorded maximum; the row-chain kernels take the scale of a
+    workgroup's own rows, between that and the scale of each row's own maximum."""
+    if not dz.size:
+        return
+    _assert_split(dz, hg_scale_for(np.abs(dz).max()), what)
+    _assert_split(dz, hg_scale_for(np.abs(dz).max(1, keepdims=True)), what + ' (row scale)')
+
+
+def _check_sums(bound, what):
+    assert bound.max(initial=0) < ACC_MAX, f'{what}: sums of |terms| up to {bound.max()} >= 2^24'
+
+
+# ---- ELU nets
+def elu_train_reference(W, b, x, dy):
+    """torch autograd in float64: y, [(dW, db)] per layer, and each layer's input X and output gradient dZ (float64 numpy)."""
+    h = torch.from_numpy(np.asarray(x, np.float64))
+    Wt = [_t64(w).requires_grad_() for w in W]; bt = [_t64(v).requires_grad_() for v in b]
+    Xs, Zs = [], []
+    for l in range(len(W)):
+        Xs.append(h)
+        z = torch.nn.functional.linear(h, Wt[l], bt[l])
+        z.retain_grad(); Zs.append(z)
+        h = torch.nn.functional.elu(z) if l < len(W) - 1 else z
+    h.backward(_t64(dy))
+    return (h.detach().numpy(), [(w.grad.numpy(), v.grad.numpy()) for w, v in zip(Wt, bt)],
+            [X.detach().numpy() for X in Xs], [z.grad.numpy() for z in Zs])
+
+
+def certify_elu_train(W, b, x, dy, lim=LIM['f32']):
+    """Forward as certify_elu (pre-activations >= 0: ELU' = 1), then the backward: every dZ, dX, dW, db an integer; the input-gradient
+    products (sum_k |dZ_k| |W_kj| per row) and the weight-gradient reductions over ALL rows (sum_r |dZ_r| |X_r|, db: sum_r |dZ_r|) below 2^24;
+    every gradient operand survives the fp16 split at the scales the kernels can choose, every activation operand at scale 1.  Returns the
+    reference (y, grads)."""
+    h = np.asarray(x, np.float64)
+    for l in range(len(W)):
+        _assert_split(h, 1.0, f'layer {l} input')
+        h = check_layer(h, W[l], b[l], lim, f'layer {l}', elu=l < len(W) - 1)
+    y, grads, Xs, dZs = elu_train_reference(W, b, x, dy)
+    np.testing.assert_array_equal(h, y)
+    for l in range(len(W)):
+        dz, X = dZs[l], Xs[l]
+        assert _is_int(dz) and _is_int(grads[l][0]) and _is_int(grads[l][1]), f'layer {l}: non-integer gradient'
+        _check_sums(np.abs(dz).T @ np.abs(X), f'layer {l} dW')
+        _check_sums(np.abs(dz).sum(0), f'layer {l} db')
+        if l:
+            _check_sums(np.abs(dz) @ np.abs(W[l]), f'layer {l} dX')
+        if l < len(W) - 1:                 # the output layer's gradient (dy) meets the exact-fp32 kernels only
+            _split_hgemm(dz, f'layer {l} dZ')
+    return y, grads
+
+
+# ---- the fine net (NeRF class, trainer layout)
+def _nerf_layers(Ws, bs, e, ev):
+    """Trainer-order forward of the NeRF class on float64 tensors: (raw, [X_l], [Z_l]) for the 12 layers (pts0..7, feature, alpha, views, rgb)."""
+    Xs, Zs = [None] * 12, [None] * 12
+
+    def lin(l, X):
+        Xs[l] = X
+        Zs[l] = torch.nn.functional.linear(X, Ws[l], bs[l])
+        return Zs[l]
+    h = e
+    for i in range(8):
+        h = torch.relu(lin(i, h))
+        if i == 4:
+            h = torch.cat([e, h], -1)
+    f = lin(8, h)
+    a = lin(9, h)
+    hv = torch.relu(lin(10, torch.cat([f, ev], -1)))
+    rgb = lin(11, hv)
+    return torch.cat([rgb, a], -1), Xs, Zs
+
+
+class NerfTrainRef:
+    """The fine net's forward / backward in float64 for one input set (pts [n, S, 3], rays [n, 11]) over its DISTINCT rows (integer points in a
+    small box, axis view directions: a few thousand): activations X_l(u), pre-activations and the Jacobians d raw / d Z_l and d raw / d pts per
+    distinct row u.  A row's gradients are then dy_r J(u_r) — exact in float64 — and a weight gradient sum_r dZ_r^T X(u_r) = sum_u (sum over
+    u's rows of dZ_r)^T X(u): one reference per (net, row count) for any number of output gradients and kernel configurations."""
+
+    def __init__(self, Ws, bs, inp):
+        n, S = inp['pts'].shape[:2]
+        self.R = n * S
+        rows = np.concatenate([inp['pts'].reshape(-1, 3), np.repeat(inp['rays'][:, 8:11], S, 0)], 1).astype(np.float64)
+        self.keys, self.inv = np.unique(rows, axis=0, return_inverse=True)
+        self.inv = self.inv.reshape(-1)
+        p = torch.from_numpy(self.keys[:, :3].copy()).requires_grad_()
+        v = torch.from_numpy(self.keys[:, 3:].copy())
+        self.W = [np.asarray(W, np.float64) for W in Ws]
+        raw, Xs, Zs = _nerf_layers([_t64(W) for W in Ws], [_t64(x) for x in bs], orc.posenc(p, MULTIRES), orc.posenc(v, MULTIRES_V))
+        for Z in Zs:
+            Z.retain_grad()
+        self.J, self.Jp = [[] for _ in range(12)], []
+        for o in range(4):
+            for Z in Zs:
+                Z.grad = None
+            p.grad = None
+            raw[:, o].sum().backward(retain_graph=o < 3)
+            for l in range(12):
+                self.J[l].append(Zs[l].grad.numpy().copy())
+            self.Jp.append(p.grad.numpy().copy())
+        self.J = [np.stack(j) for j in self.J]                 # [4, U, out_l]
+        self.Jp = np.stack(self.Jp)                            # [4, U, 3]
+        self.X = [X.detach().numpy() for X in Xs]              # [U, in_l]
+        self.raw_u = raw.detach().numpy()
+        w = {'pts_linears': [(Ws[i], bs[i]) for i in range(8)], 'feature_linear': (Ws[8], bs[8]), 'alpha_linear': (Ws[9], bs[9]),
+             'views_linears': [(Ws[10], bs[10])], 'rgb_linear': (Ws[11], bs[11])}
+        t = lambda wb: (_t64(wb[0]), _t64(wb[1]))
+        w64 = {'pts_linears': [t(x) for x in w['pts_linears']], 'views_linears': [t(w['views_linears'][0])],
+               **{k: t(w[k]) for k in ('feature_linear', 'alpha_linear', 'rgb_linear')}}
+        e, ev = orc.posenc(p.detach(), MULTIRES), orc.posenc(v, MULTIRES_V)
+        np.testing.assert_array_equal(self.raw_u, orc.nerfcls_forward(w64, torch.cat([e, ev], -1)).numpy())   # the trainer layout is the oracle's net
+
+    def raw(self):
+        return self.raw_u[self.inv]
+
+    def dz(self, l, dy, rows=None):
+        """dZ_l per row [R, out_l] for the output gradient dy [R, 4]; rows: only those rows (dy [len(rows), 4])."""
+        inv = self.inv if rows is None else self.inv[rows]
+        return np.einsum('ro,oru->ru', np.asarray(dy, np.float64), self.J[l][:, inv])
+
+    def grads(self, dy):
+        """[(dW_l, db_l)] for the 12 layers and d_pts [R, 3]."""
+        dy = np.asarray(dy, np.float64)
+        agg = np.zeros((len(self.keys), 4))
+        np.add.at(agg, self.inv, dy)
+        out = []
+        for l in range(12):
+            A = np.einsum('uo,ouj->uj', agg, self.J[l])
+            out.append((A.T @ self.X[l], A.sum(0)))
+        return out, np.einsum('ro,orc->rc', dy, self.Jp[:, self.inv])
+
+    def exact_cols(self, l):
+        """Columns of layer l's weight gradient that are exact: those whose input column holds integers in every row (the raw coordinates,
+        sin / cos of a coordinate that is 0, every hidden column); the others meet sin / cos of non-zero coordinates."""
+        X = self.X[l]
+        return np.all(X == np.round(X), axis=0)
+
+
+def _tb_cmax(Ws):
+    """tchain_norms_body: largest column sum of squares per backward stream layer (views^T feature columns, [feature; alpha]^T, pts7^T ..
+    pts1^T, pts5^T over its hidden columns)."""
+    W = [np.asarray(w, np.float64) for w in Ws]
+    cm = [(W[10][:, :256] ** 2).sum(0).max(), (np.concatenate([W[8], W[9]], 0) ** 2).sum(0).max()]
+    for L in (7, 6, 5, 4, 3, 2, 1):
+        cm.append(((W[L][:, 63:] if L == 5 else W[L]) ** 2).sum(0).max())
+    return cm
+
+
+def certify_nerf_train(ref, dy, what=''):
+    """Certificate of one fine-net call (forward on the distinct rows, backward per row for dy [R, 4]):
+      * forward: every product integer, representable, partial sums < 2^24 (check_layer), every activation operand survives the split at scale 1;
+      * every dZ_l, dX_l (= dZ_l W_l), dW_l, db_l an integer (dW: on the exact columns), the input-gradient sums sum_k |dZ_k| |W_kj| per row and
+        the weight-gradient sums sum_r |dZ_r| |X_r| over ALL R rows (exact columns; db: sum_r |dZ_r|) below 2^24;
+      * every gradient operand survives the split: at the tensor-maximum scale (hgemm_kernel, dwh_*) and at the engine backward's per-row scales —
+        the row maximum into [2^13, 2^14), then per layer the SMALLEST factor t its norm bound allows (sqrt(n2 cmax) t >= 2^12, one binade below
+        the kernel's choice for the fp32 rounding of n2) and the largest (sqrt(n2 cmax) t < 2^14).
+    Returns (raw, grads, d_pts) of the reference."""
+    Ws = ref.W
+    for l in range(12):
+        fi = Ws[l].shape[1]
+        X = ref.X[l]
+        check_layer(X, Ws[l], np.zeros(Ws[l].shape[0]), LIM['f16'], f'{what} fwd layer {l}')
+        _assert_split(X[:, np.any(Ws[l] != 0, axis=0)], 1.0, f'{what} fwd layer {l} input')
+        assert X.shape[1] == fi
+    dy = np.asarray(dy, np.float64)
+    assert _is_int(dy)
+    grads, dpts = ref.grads(dy)
+    cm = _tb_cmax(Ws)
+    rows = np.flatnonzero(np.any(dy != 0, 1))          # a row whose dy is 0 has dZ = 0 in every layer: no term, nothing to split
+    inv = ref.inv[rows]
+    dzs = {}
+    for l in range(12):
+        dz = ref.dz(l, dy[rows], rows)
+        dzs[l] = dz
+        assert _is_int(dz), f'{what} layer {l}: non-integer dZ'
+        ex = ref.exact_cols(l)
+        assert _is_int(grads[l][0][:, ex]) and _is_int(grads[l][1]), f'{what} layer {l}: non-integer dW / db'
+        B = np.zeros((len(ref.keys), dz.shape[1]))
+        np.add.at(B, inv, np.abs(dz))
+        _check_sums((B.T @ np.abs(ref.X[l]))[:, ex], f'{what} layer {l} dW')
+        _check_sums(np.abs(dz).sum(0), f'{what} layer {l} db')
+        _check_sums(np.abs(dz) @ np.abs(Ws[l]), f'{what} layer {l} dX')
+        assert _is_int(dz @ Ws[l])
+        if l != 11:                     # rgb's dZ is d raw: it meets the exact-fp32 head kernels only
+            _split_hgemm(dz, f'{what} layer {l} dZ')
+    assert _is_int(dpts[:, nerf_dpts_exact_cols(Ws, ref)])
+    # the engine backward's planes: s0 = dZ of views (128), then d feature, dZ7 .. dZ0 (stream layers s0 .. s8); alpha gradient rides along
+    chain = [dzs[10], dzs[8], dzs[7], dzs[6], dzs[5], dzs[4], dzs[3], dzs[2], dzs[1], dzs[0]]
+    m = np.abs(chain[0]).max(1)
+    s_lo = np.where(m > 0, np.ldexp(1.0, 13 - np.floor(np.log2(np.where(m > 0, m, 1))).astype(np.int64)), 1.0)
+    s_hi = s_lo.copy()
+    da = np.abs(dy[rows, 3])
+    for i, v in enumerate(chain):
+        if i:
+            sq = (chain[i - 1] ** 2).sum(1) + (da ** 2 if i == 2 else 0.0)     # s1's inputs: d feature and the alpha gradient's plane
+            n2_lo, n2_hi = sq * s_lo ** 2, sq * s_hi ** 2
+            b_lo, b_hi = np.sqrt(n2_lo * cm[i - 1]), np.sqrt(n2_hi * cm[i - 1])
+            t_lo = np.where(b_lo > 0, _pow2_floor(np.where(b_lo > 0, 2.0 ** 12 / np.maximum(b_lo, 1e-300), 1)), 1.0)
+            if i == 1:                  # s0's outputs also hold the alpha gradient: its factor is capped by |da| s0 t < 2^14
+                cap = np.where(da > 0, _pow2_floor(np.where(da > 0, 2.0 ** 13 / np.maximum(da * s_lo, 1e-300), 1)), np.inf)
+                t_lo = np.minimum(t_lo, cap)
+            t_hi = np.where(b_hi > 0, 2.0 ** 14 / np.maximum(b_hi, 1e-300), 1.0)
+            s_lo, s_hi = s_lo * t_lo, s_hi * _pow2_floor(t_hi)
+        _assert_split(v, s_lo[:, None], f'{what} engine plane {i} (smallest scale)')
+        if i == 1:
+            _assert_split(da, s_lo, f'{what} engine alpha plane (smallest scale)')
+        assert np.all(np.abs(v) * s_hi[:, None] < 2.0 ** 14 * 4), f'{what} engine plane {i}: overflow at the largest scale'
+    return ref.raw(), grads, dpts
+
+
+def nerf_dpts_exact_cols(Ws, ref):
+    """Coordinates c of d_pts that are exact: c is 0 in every sample, or no weight of pts0 / of the skip layer's embedding columns meets c's
+    sin / cos columns (d e / d x_c then carries only the raw column's integer gradient: cos(.) 0 - sin(.) 0 = 0 exactly)."""
+    pts = ref.keys[:, :3]
+    return np.array([bool(np.all(pts[:, c] == 0) or (np.all(Ws[0][:, pe_cols(c, MULTIRES)] == 0) and np.all(Ws[5][:, pe_cols(c, MULTIRES)] == 0)))
+                     for c in range(3)])
+
+
+def dpts_sums(ref, dy):
+    """posenc_bwd's sum of |terms| per row and coordinate [R, 3]: g = sum over pts0's and the skip layer's embedding gradient e of
+    e_c + sum_k 2^k (cos(2^k x) e_sin,k - sin(2^k x) e_cos,k).  Where it is below 2^24 d_pts is exact (cos 0 = 1, sin 0 = 0 on the live
+    coordinate; zero e on the others); elsewhere fp32 rounds it (d_pts_bound)."""
+    dy = np.asarray(dy, np.float64)
+    rows = np.flatnonzero(np.any(dy != 0, 1))
+    T = np.zeros((ref.R, 3))
+    f = np.concatenate([[1.0], np.repeat(2.0 ** np.arange(MULTIRES), 2)])
+    for l, cols in ((0, slice(0, 63)), (5, slice(0, 63))):
+        e = np.abs(ref.dz(l, dy[rows], rows) @ ref.W[l][:, cols])
+        for c in range(3):
+            T[rows, c] += e[:, [c] + [3 + 6 * k + c + 3 * h for k in range(MULTIRES) for h in (0, 1)]] @ f
+    return T
+
+
+def dpts_bound(T):
+    """|got - ref| of d_pts where its sum of |terms| T reaches 2^24: 2 x 21 terms, each a product and a difference rounded (<= 3 roundings),
+    and 42 additions, each rounding by <= 2^-24 of a partial sum <= T: (3 + 42) 2^-24 T, taken as 48 2^-24 T."""
+    return np.where(T < ACC_MAX, 0.0, 48.0 * 2.0 ** -24 * T)
+
+
+def dw_inexact_bound(ref, l, dy, splits=132):
+    """Componentwise bound for the weight-gradient columns that meet sin / cos of non-zero coordinates (tests/test_exact_train_gpu.py docstring):
+    sum_r |dZ_r| (E_SIN + 2^-23 + (nnz + splits) 2^-24 (|X_r| + E_SIN + 2^-23)), nnz = nonzero rows of dZ in that output; db needs none."""
+    rows = np.flatnonzero(np.any(np.asarray(dy) != 0, 1))
+    dz = np.abs(ref.dz(l, np.asarray(dy)[rows], rows))
+    B = np.zeros((len(ref.keys), dz.shape[1]))
+    np.add.at(B, ref.inv[rows], dz)
+    nnz = (dz != 0).sum(0)[:, None]
+    e = E_SIN + 2.0 ** -23
+    return B.sum(0)[:, None] * e + (nnz + splits) * 2.0 ** -24 * (B.T @ (np.abs(ref.X[l]) + e))

@@ -97,6 +97,9 @@ def test_argument_errors_are_reported(lib):
     with pytest.raises(_lib.PnrfError):
         _lib.check(rc, 'posenc')
     assert lib.pnrf_posenc_fwd(None, None, 0, 10, None) == 0      # empty input is a no-op
+    # the trainer's operator-level entry point refuses a missing trainer before any device work (the other checks need one: test_exact_train_gpu.py)
+    assert lib.pnrf_trainer_net_fwd_bwd(None, 0, None, None, 1, 1, None, None, None, None) == -1
+    assert b'pnrf_trainer_net_fwd_bwd' in lib.pnrf_last_error()
 
 
 def test_engine_images_are_validated_before_any_device_work(lib):
