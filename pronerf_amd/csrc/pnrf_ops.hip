@@ -447,6 +447,12 @@ __global__ __launch_bounds__(256) void explore_kernel(ExploreArgs a, const float
 }
 
 // ---------------------------------------------------------------- raw2outputs (trt.py:564-597; base.py:501-551; refine2.py:475-522)
+// disp_map = 1 / max(1e-10, depth / acc) with torch.max's NaN: a ray that composites nothing (acc = 0, depth = 0) gets 0 / 0 = NaN, which
+// torch.max passes on and fmaxf would replace by 1e-10
+__device__ __forceinline__ float disp_of(float sd, float sa) {
+  const float q = ieee_div(sd, sa);
+  return ieee_div(1.f, q != q ? q : fmaxf(1e-10f, q));
+}
 // One thread per ray: the form for many rays (from 65 536 on every SIMD has waves to hide the latencies with).
 __global__ void composite_thread_kernel(const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int d_stride,
                                  const float* __restrict__ add, const float* __restrict__ mul, const float* __restrict__ noise, float clampv,
@@ -505,7 +511,7 @@ __global__ void composite_thread_kernel(const float* __restrict__ raw, const flo
     if (rgb) { rgb[i * 3] = s0; rgb[i * 3 + 1] = s1; rgb[i * 3 + 2] = s2; }
     if (depth) depth[i] = sd;
     if (acc_out) acc_out[i] = sa;
-    if (disp) disp[i] = ieee_div(1.f, fmaxf(1e-10f, ieee_div(sd, sa)));
+    if (disp) disp[i] = disp_of(sd, sa);
   }
 }
 
@@ -566,7 +572,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     if (rgb) { rgb[i * 3] = s0; rgb[i * 3 + 1] = s1; rgb[i * 3 + 2] = s2; }
     if (depth) depth[i] = sd;
     if (acc_out) acc_out[i] = sa;
-    if (disp) disp[i] = ieee_div(1.f, fmaxf(1e-10f, ieee_div(sd, sa)));
+    if (disp) disp[i] = disp_of(sd, sa);
   }
 }
 

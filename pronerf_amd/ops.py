@@ -34,6 +34,15 @@ def _chk(t, name, shape_tail=None):
     return t.contiguous()
 
 
+def _chk_rows(t, name, width):
+    """[n, width] rows with contiguous columns and any row stride >= width, e.g. rays[:, 3:6] of the [n, 11] rays: (tensor, row stride),
+    without a copy.  Any other layout goes through _chk (checked, made contiguous; row stride = width)."""
+    if (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == f32 and t.dim() == 2 and t.shape[1] == width and t.stride(1) == 1
+            and t.stride(0) >= width):
+        return t, t.stride(0)
+    return _chk(t, name, (width,)), width
+
+
 class PackedMLP:
     """Device-resident pre-tiled weights of one network (pnrf_mlp_pack)."""
 
@@ -291,7 +300,8 @@ def refine_input(rays, or_rays, depth_sorted, img4, proj, eps=1e-5):
 
 
 def composite(raw, z, rays_d, add=None, mul=None, noise=None, clamp=0.0, white_bkgd=False):
-    raw = _chk(raw, 'raw', (4,)); z = _chk(z, 'z_vals'); rays_d = _chk(rays_d, 'rays_d', (3,))
+    """raw2outputs -> (rgb, disp, acc, weights, depth).  rays_d may be a row-strided [n, 3] view (rays[:, 3:6] of the [n, 11] rays)."""
+    raw = _chk(raw, 'raw', (4,)); z = _chk(z, 'z_vals'); rays_d, d_stride = _chk_rows(rays_d, 'rays_d', 3)
     n, s = z.shape
     add = None if add is None else _chk(add, 'mm_density_add')
     mul = None if mul is None else _chk(mul, 'mm_density_mul')
@@ -299,7 +309,7 @@ def composite(raw, z, rays_d, add=None, mul=None, noise=None, clamp=0.0, white_b
     dev = raw.device
     rgb = torch.empty(n, 3, device=dev, dtype=f32); disp = torch.empty(n, device=dev, dtype=f32)
     acc = torch.empty(n, device=dev, dtype=f32); w = torch.empty(n, s, device=dev, dtype=f32); depth = torch.empty(n, device=dev, dtype=f32)
-    check(_lib.load().pnrf_composite_fwd(_ptr(raw), _ptr(z), _ptr(rays_d), 3, _ptr(add), _ptr(mul), _ptr(noise), float(clamp),
+    check(_lib.load().pnrf_composite_fwd(_ptr(raw), _ptr(z), _ptr(rays_d), d_stride, _ptr(add), _ptr(mul), _ptr(noise), float(clamp),
                                          int(bool(white_bkgd)), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w), _ptr(depth), n, s, _stream()),
           'pnrf_composite_fwd')
     return rgb, disp, acc, w, depth
@@ -438,8 +448,9 @@ def linspace(start, end, n):
 
 # ------------------------------------------------------------------------------------------ stage-2 training step
 def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0.0, white_bkgd=False):
-    """raw2outputs backward for d rgb_map -> (d_raw, d_z, d_add, d_mul); d_add / d_mul are None without add / mul."""
-    raw = _chk(raw, 'raw', (4,)); z = _chk(z, 'z_vals'); rays_d = _chk(rays_d, 'rays_d', (3,)); d_rgb = _chk(d_rgb, 'd_rgb', (3,))
+    """raw2outputs backward for d rgb_map -> (d_raw, d_z, d_add, d_mul); d_add / d_mul are None without add / mul.  rays_d may be a
+    row-strided [n, 3] view, as in composite."""
+    raw = _chk(raw, 'raw', (4,)); z = _chk(z, 'z_vals'); rays_d, d_stride = _chk_rows(rays_d, 'rays_d', 3); d_rgb = _chk(d_rgb, 'd_rgb', (3,))
     n, s = z.shape
     add = None if add is None else _chk(add, 'mm_density_add')
     mul = None if mul is None else _chk(mul, 'mm_density_mul')
@@ -447,7 +458,7 @@ def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0
     d_raw = torch.empty_like(raw); d_z = torch.empty_like(z)
     d_add = None if add is None else torch.empty_like(z)
     d_mul = None if mul is None else torch.empty_like(z)
-    check(_lib.load().pnrf_composite_bwd(_ptr(raw), _ptr(z), _ptr(rays_d), 3, _ptr(add), _ptr(mul), _ptr(noise), float(clamp), int(bool(white_bkgd)),
+    check(_lib.load().pnrf_composite_bwd(_ptr(raw), _ptr(z), _ptr(rays_d), d_stride, _ptr(add), _ptr(mul), _ptr(noise), float(clamp), int(bool(white_bkgd)),
                                          _ptr(d_rgb), _ptr(d_raw), _ptr(d_z), _ptr(d_add), _ptr(d_mul), n, s, _stream()), 'pnrf_composite_bwd')
     return d_raw, d_z, d_add, d_mul
 

@@ -87,6 +87,11 @@ def test_linspace_matches_torch(lib):
     from pronerf_amd import ops
     for n in (1, 2, 7, 48, 64, 255):
         np.testing.assert_array_equal(ops.linspace(0.0, 1.0, n), torch.linspace(0, 1, n).numpy())
+    # the exploration offsets (pnrf_explore_fwd; orc.explore_samples): torch.linspace(0, 1 - 1/n_mult, n_mult), every n_mult, signs too
+    for n_mult in range(1, 33):
+        a, b = ops.linspace(0.0, 1 - 1 / n_mult, n_mult), torch.linspace(0, 1 - 1 / n_mult, n_mult).numpy()
+        np.testing.assert_array_equal(a, b, err_msg=f'n_mult={n_mult}')
+        np.testing.assert_array_equal(np.signbit(a), np.signbit(b), err_msg=f'n_mult={n_mult}')
 
 
 def test_argument_errors_are_reported(lib):
