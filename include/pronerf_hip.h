@@ -461,6 +461,37 @@ int pnrf_trainer_set_products(pnrf_trainer_t* t, int kind);
 int pnrf_trainer_adam_step(pnrf_trainer_t* t, int which, float lr, float beta1, float beta2, float eps,
                            float weight_decay, void* stream);
 
+/* ---- frame tail: image metrics and 8-bit output ------------------------------------------------
+ * What render_path does with a finished frame (run_S_eS_eN_alter_trt.py:350-362: PSNR against the ground truth, to8b, depth / max(depth),
+ * PNG) and the SSIM the method is reported with (run_nerf_helpers.py:151-197), on the device: the frame never travels as fp32.
+ *
+ * img2mse + img2ssim of two H x W x 3 images in one call (run_nerf_helpers.py:129, 151-197).  pred, gt: dev fp32, pixel (y, x) channel c at
+ * [(y W + x) stride + c] with the image's own pixel stride in floats (>= 3): 3 reads an [H,W,3] image, 4 the rgbd[n,4] rows of
+ * pnrf_render_rays_fwd.  taps: HOST [T], the 1-D filter (run_nerf_helpers.py:163-167 evaluated in float64, rounded to fp32), 1 <= T <= 16,
+ * applied as a convolution along y and along x with 'valid' windows (:170-175): the SSIM map has (H - T + 1) x (W - T + 1) x 3 values.
+ * Arithmetic of :176-196 in fp32: five filtered moments per channel (of the images minus max_val / 2: variances do not see the shift, the
+ * means get it back), variances clamped at 0, covariance limited to sign(s01) min(sqrt(s00 s11), |s01|), c1 = (k1 max_val)^2,
+ * c2 = (k2 max_val)^2, the quotient.  One workgroup per 32 x 32 output tile and channel (both input tiles with their halo in LDS, a pass
+ * along x into LDS, a pass along y from it), per-workgroup partial sums in fp64 into the workspace, summed in a fixed order by a second
+ * small kernel: no atomics, results bit-identical from call to call on any stream.
+ * out: dev double[4] = {sum (pred - gt)^2 over the H W 3 values, that / (H W 3) (img2mse), sum of the SSIM map, its mean (img2ssim)}.
+ * ssim_map: dev fp32 [H-T+1, W-T+1, 3] or NULL.  workspace: dev, 8-byte aligned, >= pnrf_image_metrics_workspace_bytes(H, W, T) bytes
+ * (0 for sizes the call refuses), contents irrelevant; concurrent calls need separate workspaces.  H < T, W < T, T outside 1 .. 16, a
+ * null pointer or a stride below 3 return PNRF_E_ARG. */
+int64_t pnrf_image_metrics_workspace_bytes(int H, int W, int T);
+int pnrf_image_metrics_fwd(const float* pred, int pred_stride, const float* gt, int gt_stride, int H, int W,
+                           const float* taps, int T, float max_val, float k1, float k2, double* out,
+                           float* ssim_map, void* workspace, int64_t workspace_bytes, void* stream);
+/* to8b of a frame (run_nerf_helpers.py:135; run_S_eS_eN_alter_trt.py:356, 360): rgb8[n,3] = to8b(rgb), depth8[n] = to8b(depth / max(depth)),
+ * uint8, bit-identical to numpy for finite input — 255 * clip(x, 0, 1) is one fp32 product, truncated; the quotient is one correctly
+ * rounded fp32 division by the maximum, which a first kernel takes on the device.  rgb: dev, pixel i at [i rgb_stride + c], rgb_stride >= 3;
+ * depth: dev, pixel i at [i depth_stride], depth_stride >= 1 (rgbd[n,4]: rgb = rgbd, depth = rgbd + 3, both strides 4).  Either output
+ * may be NULL (then its input may be too), not both.  workspace: dev, 4-byte aligned, >= PNRF_TO8B_WORKSPACE_BYTES (needed with depth8).
+ * Not finite input: NaN -> 0, +Inf -> 255, -Inf -> 0; the maximum skips NaN depths, and a quotient that is NaN (Inf / Inf, 0 / 0) -> 0. */
+#define PNRF_TO8B_WORKSPACE_BYTES 4096
+int pnrf_frame_to8b_fwd(const float* rgb, int rgb_stride, const float* depth, int depth_stride, int64_t n,
+                        uint8_t* rgb8, uint8_t* depth8, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Host helper: torch.linspace(start,end,n) in fp32, as used for the 48 ray points
  * (run_S_eS_eN_alter_trt.py:556-557).  out: HOST [n]. */
 int pnrf_linspace(float start, float end, int n, float* out);

@@ -69,6 +69,10 @@ SIGNATURES = {
     'pnrf_ctx_profile_begin': (_i, [_p, _i]),
     'pnrf_ctx_profile_end': (_i, [_p, C.POINTER(C.c_float), C.POINTER(_i)]),
     'pnrf_linspace': (_i, [_f, _f, _i, C.POINTER(_f)]),
+    # frame tail: image metrics and 8-bit output
+    'pnrf_image_metrics_workspace_bytes': (_i64, [_i, _i, _i]),
+    'pnrf_image_metrics_fwd': (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _p, _p, _p, _i64, _p]),
+    'pnrf_frame_to8b_fwd': (_i, [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p]),
     # stage-2 training step
     'pnrf_composite_bwd': (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
     'pnrf_posenc_bwd': (_i, [_p, _p, _p, _i64, _i, _p]),

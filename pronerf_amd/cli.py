@@ -58,6 +58,10 @@ def infer_argv(ns):
         argv.append('--use_trt')
     if ns.max_images is not None:
         argv += ['--max_images', str(ns.max_images)]
+    if getattr(ns, 'metrics', None) is not None:
+        argv += ['--metrics', ns.metrics]
+    if getattr(ns, 'device_to8b', False):
+        argv.append('--device_to8b')
     return argv + _extra(ns)
 
 
@@ -106,6 +110,10 @@ def build_parser():
     def passthrough(q):
         q.add_argument('extra', nargs=argparse.REMAINDER, help='additional arguments for the underlying driver; prefix with --')
 
+    def frame_tail(q):
+        q.add_argument('--metrics', choices=['psnr', 'psnr,ssim'], default=None, help="'psnr,ssim': PSNR and SSIM of the rendered test views, taken on the device")
+        q.add_argument('--device_to8b', '--device-to8b', action='store_true', dest='device_to8b', help='8-bit PNG planes converted on the device')
+
     q = sub.add_parser('train-stage1', help='alternating sampler / NeRF training')
     q.add_argument('--config', default='configs/llff/fern/fern_epi.txt')
     q.add_argument('--no-reload', action='store_true', dest='no_reload')
@@ -123,12 +131,14 @@ def build_parser():
     q.add_argument('--render-test', action='store_true', dest='render_test')
     q.add_argument('--use-trt', action='store_true', dest='use_trt')
     q.add_argument('--max-images', type=int, default=None, dest='max_images')
+    frame_tail(q)
     passthrough(q); q.set_defaults(func=_infer)
     q = sub.add_parser('eval', help='render the test split through the inference path')
     q.add_argument('--config', default='configs/llff/fern/fern_trt.txt')
     q.add_argument('--checkpoint', default=None)
     q.add_argument('--use-trt', action='store_true', dest='use_trt')
     q.add_argument('--max-images', type=int, default=None, dest='max_images')
+    frame_tail(q)
     passthrough(q); q.set_defaults(func=_eval)
     q = sub.add_parser('export-trt', help='write the engine files (packed weight streams) of a checkpoint')
     q.add_argument('--config', default='configs/llff/fern/fern_trt.txt')

@@ -37,7 +37,10 @@ _VARIANT = {
             ('mm_engine_path', str, None), ('refine_engine_path', str, None), ('max_images', int, None),
             # not in the reference: the renderer's operating point (pronerf_amd.render.PRESETS) — 'default', 'quality' (exact sampler + fp16 NeRF
             # operands) or 'auto' (decided from the first rendered frame: the exact single-pass sampler when the two-pass form would re-render most rays)
-            ('pnrf_preset', str, 'default')],
+            ('pnrf_preset', str, 'default'),
+            # not in the reference: 'psnr,ssim' takes PSNR and SSIM of the hold-out views on the device (render_path's pnrf_metrics); device_to8b hands
+            # the PNG writer 8-bit planes converted on the device (pnrf_device_to8b)
+            ('metrics', str, 'psnr'), ('device_to8b', 'flag', False)],
     # stage 2 (run_S_eS_eN_alter_base_refine2.py)
     'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)],
     # stage 1 (run_S_eS_eN_alter_base.py)

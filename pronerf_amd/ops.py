@@ -446,6 +446,96 @@ def linspace(start, end, n):
     return np.array(out[:], dtype=np.float32)
 
 
+# ------------------------------------------------------------------------------------------ frame tail: image metrics, 8-bit output
+def ssim_filter(filter_size=11, filter_sigma=1.5):
+    """The 1-D Gaussian of img2ssim in float64 (helpers:163-167): ``filter_size`` taps spaced 1 apart and centred on 0 — an even size sits
+    half a tap off the pixel grid —, exp(-x^2 / (2 sigma^2)), normalised to sum 1.  The kernel takes it rounded to fp32."""
+    half = int(filter_size) // 2
+    offset = (2 * half - int(filter_size) + 1) / 2            # 0 for an odd size, 0.5 for an even one
+    x = (np.arange(int(filter_size)) - half + offset) / filter_sigma
+    g = np.exp(-0.5 * x ** 2)
+    return g / g.sum()
+
+
+def _pixels(t, name, width):
+    """A tensor whose last dimension holds ``width`` contiguous floats per pixel (width 0: the tensor's elements are the pixels) and whose
+    pixels lie a constant number of floats apart — [H,W,3], [n,3], or such a view into rgbd[n,4] — as (tensor, pixel stride, pixel count)
+    without a copy; any other layout is made contiguous."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PnrfError(f'{name}: expected a GPU tensor (pronerf_amd has no CPU path)')
+    if t.dtype != f32:
+        raise PnrfError(f'{name}: expected float32, got {t.dtype}')
+    if width and (t.dim() < 2 or t.shape[-1] != width):
+        raise PnrfError(f'{name}: expected trailing shape ({width},), got {tuple(t.shape)}')
+    lead = t.shape[:-1] if width else t.shape
+    strides = t.stride()[:-1] if width else t.stride()
+    n = int(np.prod(lead, dtype=np.int64))
+    ok = (not width or t.stride(-1) == 1) and len(lead) >= 1 and strides[-1] >= max(width, 1)
+    for d in range(len(lead) - 1):
+        ok = ok and (lead[d] == 1 or strides[d] == strides[d + 1] * lead[d + 1])
+    if ok:
+        return t, int(strides[-1]), n
+    return t.contiguous(), max(width, 1), n
+
+
+def image_metrics(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """img2mse and img2ssim of two [H,W,3] images in one call (pnrf_image_metrics_fwd; helpers:129, 151-197).  ``pred`` / ``gt`` may be
+    views with a pixel stride above 3, e.g. ``rgbd[:, :3].reshape(H, W, 3)`` of the renderer's [n,4] rows.  Returns a float64 device tensor
+    [4] = (sum of squared differences, mse, sum of the SSIM map, mean SSIM) — nothing is read back — and, with ``return_map``, also the
+    [H-T+1, W-T+1, 3] SSIM map."""
+    lib = _lib.load()
+    if pred.dim() != 3 or pred.shape[-1] != 3 or pred.shape != gt.shape:
+        raise PnrfError(f'image_metrics: expected two [H,W,3] images of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}')
+    H, W = int(pred.shape[0]), int(pred.shape[1])
+    T = int(filter_size)
+    if not 1 <= T <= 16 or H < T or W < T:
+        raise PnrfError(f'image_metrics: filter_size {T} must be 1 .. 16 and fit the {H} x {W} image')
+    pred, sp, _ = _pixels(pred, 'pred', 3)
+    gt, sg, _ = _pixels(gt, 'gt', 3)
+    if gt.device != pred.device:
+        raise PnrfError('image_metrics: pred and gt are on different devices')
+    taps = np.ascontiguousarray(ssim_filter(T, filter_sigma), dtype=np.float32)
+    with torch.cuda.device(pred.device):
+        nb = int(lib.pnrf_image_metrics_workspace_bytes(H, W, T))
+        ws = torch.empty(nb // 8, device=pred.device, dtype=torch.float64)
+        out = torch.empty(4, device=pred.device, dtype=torch.float64)
+        smap = torch.empty(H - T + 1, W - T + 1, 3, device=pred.device, dtype=f32) if return_map else None
+        check(lib.pnrf_image_metrics_fwd(_ptr(pred), sp, _ptr(gt), sg, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), T, float(max_val), float(k1),
+                                         float(k2), _ptr(out), _ptr(smap), _ptr(ws), nb, _stream()), 'pnrf_image_metrics_fwd')
+    return (out, smap) if return_map else out
+
+
+def frame_to8b(rgb=None, depth=None, rgbd=None):
+    """to8b(rgb) and to8b(depth / max(depth)) as uint8 device tensors (pnrf_frame_to8b_fwd; helpers:135, trt.py:356-360), bit-identical to
+    numpy for finite input (NaN -> 0).  ``rgbd`` [n,4] (the renderer's rows), or ``rgb`` [..., 3] and / or ``depth`` [...] — views into
+    rgbd are taken as they are.  Returns (rgb8 shaped like rgb, depth8 shaped like depth); an input that is None gives None."""
+    lib = _lib.load()
+    if rgbd is not None:
+        if rgb is not None or depth is not None or rgbd.dim() != 2 or rgbd.shape[-1] != 4:
+            raise PnrfError('frame_to8b: rgbd must be [n,4] and excludes rgb / depth')
+        rgb, depth = rgbd[:, :3], rgbd[:, 3]
+    if rgb is None and depth is None:
+        raise PnrfError('frame_to8b: nothing to convert')
+    n = None
+    if rgb is not None:
+        shape_rgb = tuple(rgb.shape)
+        rgb, sr, n = _pixels(rgb, 'rgb', 3)
+    if depth is not None:
+        shape_d = tuple(depth.shape)
+        depth, sd, nd = _pixels(depth, 'depth', 0)
+        if n is not None and nd != n:
+            raise PnrfError(f'frame_to8b: {n} rgb pixels but {nd} depths')
+        n = nd
+    dev = (rgb if rgb is not None else depth).device
+    with torch.cuda.device(dev):
+        rgb8 = torch.empty(shape_rgb, device=dev, dtype=torch.uint8) if rgb is not None else None
+        depth8 = torch.empty(shape_d, device=dev, dtype=torch.uint8) if depth is not None else None
+        ws = torch.empty(1024, device=dev, dtype=f32) if depth is not None else None
+        check(lib.pnrf_frame_to8b_fwd(_ptr(rgb), sr if rgb is not None else 0, _ptr(depth), sd if depth is not None else 0, n, _ptr(rgb8), _ptr(depth8),
+                                      _ptr(ws), 4096 if ws is not None else 0, _stream()), 'pnrf_frame_to8b_fwd')
+    return rgb8, depth8
+
+
 # ------------------------------------------------------------------------------------------ stage-2 training step
 def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0.0, white_bkgd=False):
     """raw2outputs backward for d rgb_map -> (d_raw, d_z, d_add, d_mul); d_add / d_mul are None without add / mul.  rays_d may be a

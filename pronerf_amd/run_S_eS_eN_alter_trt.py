@@ -350,7 +350,12 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     timed ``render()`` calls bracketed by device events (:327-332), PSNR and PNG output.
     ``render_kwargs`` needs ``poses`` [n,3,4], ``images`` [n,H,W,3], ``ref_K`` in addition to the
     ``create_nerf`` entries.  Returns (rgbs0, rgbs1, depths, depths) and stores the per-frame
-    milliseconds in ``render_kwargs['render_ms']``."""
+    milliseconds in ``render_kwargs['render_ms']``.
+
+    Two opt-in entries of ``render_kwargs`` move the frame's tail to the device (both off: the statements of the reference):
+    ``pnrf_metrics`` takes PSNR and SSIM (helpers:151-197) of every pose against ``gt_imgs[i]`` from one ``ops.image_metrics`` call on the
+    rendered rows, read back together, into ``render_kwargs['psnrs']`` / ``['ssims']``; ``pnrf_device_to8b`` encodes a pose's two PNGs
+    from ``ops.frame_to8b``'s uint8 planes (same bytes as ``to8b`` on the host).  The returned float arrays are the same either way."""
     H, W, focal = hwf
     if render_factor != 0:
         H, W, focal = H // render_factor, W // render_factor, focal / render_factor
@@ -363,6 +368,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     ref_Kh = np.asarray(ref_K.detach().cpu() if isinstance(ref_K, torch.Tensor) else ref_K, dtype=np.float32)
     dev = next(render_kwargs['network_fine'].parameters()).device
     rgbs0, rgbs1, depths, psnrs, times, walls = [], [], [], [], [], []
+    dev_metrics, dev_to8b, ssims = bool(render_kwargs.get('pnrf_metrics')), bool(render_kwargs.get('pnrf_device_to8b')), []
     from concurrent.futures import ThreadPoolExecutor
     from .dist import FrameGather, world as _world
     from .render import RayPartition
@@ -433,11 +439,21 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         times.append(frame_ms)
         rgbs0.append(rgb0.cpu().numpy()); rgbs1.append(rgb1.cpu().numpy()); depths.append(depth_map.cpu().numpy())
         if gt_imgs is not None and render_factor == 0:
-            psnrs.append(mse2psnr(img2mse(rgb1, torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev))))
+            if dev_metrics:      # img2mse + img2ssim in one call on the frame where it lies (rgb1 is a view of the [n, 4] rows), one read-back of both
+                m = ops.image_metrics(rgb1, torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev)).cpu()
+                psnrs.append(float(mse2psnr(m[1]))); ssims.append(float(m[3]))
+            else:
+                psnrs.append(mse2psnr(img2mse(rgb1, torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev))))
         if png_pool is not None:
             os.makedirs(savedir, exist_ok=True)
-            png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgbs1[-1])))
-            png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, 'depth_{:03d}.png'.format(i)), to8b(depths[-1] / np.max(depths[-1]))))
+            if dev_to8b:         # the two 8-bit planes come from the device into pinned memory: 4 bytes per pixel instead of 16, no to8b / np.max on the host
+                planes = [torch.empty(t.shape, dtype=torch.uint8).pin_memory().copy_(t, non_blocking=True) for t in ops.frame_to8b(rgb1, depth_map)]
+                torch.cuda.current_stream(dev).synchronize()
+                png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, '{:03d}.png'.format(i)), planes[0].numpy()))
+                png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, 'depth_{:03d}.png'.format(i)), planes[1].numpy()))
+            else:
+                png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgbs1[-1])))
+                png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, 'depth_{:03d}.png'.format(i)), to8b(depths[-1] / np.max(depths[-1]))))
         walls.append((time.perf_counter() - tw) * 1e3)
     for j in png_jobs:
         j.result()                                                      # re-raises a writer's exception
@@ -449,6 +465,10 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         print(psnrs)
         print(f'Mean Test PSNR {float(sum(psnrs) / len(psnrs))}')
     render_kwargs['psnrs'] = [float(p) for p in psnrs]
+    if dev_metrics:
+        if len(ssims) > 0 and verbose:
+            print(f'Mean Test SSIM {sum(ssims) / len(ssims)}')
+        render_kwargs['ssims'] = ssims
     return np.stack(rgbs0, 0), np.stack(rgbs1, 0), np.stack(depths, 0), np.stack(depths, 0)
 
 
@@ -516,6 +536,11 @@ def train(argv=None, device='cuda'):
         kw['use_trt'] = True
     kw.update({'near': near, 'far': far, 'images': images[i_ref], 'poses': poses[i_ref], 'ref_K': K})   # :773-787
     kw['pnrf_preset'] = getattr(args, 'pnrf_preset', 'default')
+    metrics = [m for m in str(getattr(args, 'metrics', 'psnr')).split(',') if m]
+    if not set(metrics) <= {'psnr', 'ssim'}:
+        raise PnrfError(f"--metrics takes 'psnr' or 'psnr,ssim', got {args.metrics!r}")
+    kw['pnrf_metrics'] = 'ssim' in metrics
+    kw['pnrf_device_to8b'] = bool(getattr(args, 'device_to8b', False))
     if args.max_images is not None:
         i_test = i_test[:args.max_images]
     if args.render_test:

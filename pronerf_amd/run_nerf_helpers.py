@@ -11,6 +11,7 @@ Same names, argument meaning and error behaviour as the live subset of the refer
     DoNeRFTRT                      helpers:1186-1343 -> pnrf_mlp_fwd (bf16 MFMA)
     NeRF                           helpers:792-847   -> pnrf_mlp_fwd (bf16 MFMA, skip + view branch)
     get_rays / ndc_rays            helpers:2705-2714, 2776-2793 -> pnrf_frame_rays_fwd / pnrf_ndc_rays_fwd
+    img2ssim                       helpers:151-197   -> pnrf_image_metrics_fwd
 
 The model classes keep the reference's ``state_dict`` keys (``fc_backbone.{i}.*``, ``fc_output.*``,
 ``layers.{i}.*``) so checkpoints interchange; their parameters are re-packed into the device weight
@@ -29,7 +30,28 @@ from .ops import PnrfError
 # Misc (helpers:129-135) — frame-level metrics on finished images, not part of the per-ray path
 img2mse = lambda x, y: torch.mean((x - y) ** 2)
 mse2psnr = lambda x: -10. * torch.log10(x)
+img2mse_np = lambda x, y: np.mean((x - y) ** 2)
+mse2psnr_np = lambda x: -10. * np.log10(x)
 to8b = lambda x: (255 * np.clip(x, 0, 1)).astype(np.uint8)
+
+
+def img2ssim(img0, img1, max_val=1, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """The mip-NeRF SSIM of two [H,W,3] images (helpers:151-197): 1-D Gaussian of ``filter_size`` taps applied along both axes with 'valid'
+    windows, clamped variances, limited covariance -> pnrf_image_metrics_fwd.  numpy arrays (uploaded) or torch tensors; returns the mean as a
+    Python float or, with ``return_map``, the [H-T+1, W-T+1, 3] map — a numpy array for numpy input, else a tensor on the GPU.  fp32 on the
+    device where the reference runs float64 on the host (errors per case: DESIGN.md §4.8).  No CPU path: PnrfError without the library."""
+    assert len(img0.shape) == 3
+    assert img0.shape[-1] == 3
+    assert img0.shape == img1.shape
+    from . import _lib
+    _lib.load()
+    host = not isinstance(img0, torch.Tensor)
+    dev = next((t.device for t in (img0, img1) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device('cuda'))
+    a, b = (torch.as_tensor(np.ascontiguousarray(t) if not isinstance(t, torch.Tensor) else t).to(device=dev, dtype=torch.float32) for t in (img0, img1))
+    res = ops.image_metrics(a, b, max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2, return_map=return_map)
+    if return_map:
+        return res[1].cpu().numpy() if host else res[1]
+    return float(res[3])
 
 
 # ------------------------------------------------------------------------------- encodings
