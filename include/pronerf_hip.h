@@ -42,6 +42,7 @@ extern "C" {
 typedef struct pnrf_mlp pnrf_mlp_t;
 typedef struct pnrf_ctx pnrf_ctx_t;
 typedef struct pnrf_trainer pnrf_trainer_t;
+typedef struct pnrf_scene pnrf_scene_t;
 
 int pnrf_abi_version(void);
 const char* pnrf_last_error(void);
@@ -491,6 +492,57 @@ int pnrf_image_metrics_fwd(const float* pred, int pred_stride, const float* gt, 
 #define PNRF_TO8B_WORKSPACE_BYTES 4096
 int pnrf_frame_to8b_fwd(const float* rgb, int rgb_stride, const float* depth, int depth_stride, int64_t n,
                         uint8_t* rgb8, uint8_t* depth8, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- device-resident scene: a frame from a camera pose alone ---------------------------------------
+ * What render_path does per pose on the host (run_S_eS_eN_alter_trt.py:245-302: rank the source cameras, fetch / permute / upload the neighbour
+ * images, build the projection matrices, build the rays) from a scene that lives on the device.  The source views are fixed, so they are uploaded
+ * once; per target pose only O(views) arithmetic and one copy of the nb selected images remain, all of it kernels of this library reading the pose
+ * from DEVICE memory: no host read-back, no allocation, capturable in a hipGraph that is replayed with twelve floats changed.
+ *
+ * A scene holds nv source views of Hf x Wf pixels: the texel cache [nv,Hf,Wf,4] (PNRF_SCENE_F32: float4 texels, exact for any image;
+ * PNRF_SCENE_U8: RGBA8 texels, a quarter of the memory, for 8-bit sources), their camera-to-world poses [nv,3,4] and two 3 x 3 intrinsics.
+ * 1 <= nv <= 4096.  pnrf_scene_create validates and does NO device work; the device arrays (one allocation) are made on the current device by the
+ * first pnrf_scene_set_view / pnrf_scene_set_intrinsics, and the scene then belongs to that device (PNRF_E_STATE from another one).  A scene is
+ * configuration like a packed network: set every view and the intrinsics, then use it; the forward calls do not change it. */
+#define PNRF_SCENE_F32 0
+#define PNRF_SCENE_U8 1
+#define PNRF_IMG_F32 0
+#define PNRF_IMG_U8 1
+int pnrf_scene_create(int nv, int Hf, int Wf, int format, pnrf_scene_t** out);
+int pnrf_scene_free(pnrf_scene_t* s);
+/* Source view v: img dev [Hf,Wf,pix_stride], fp32 (PNRF_IMG_F32) or uint8 (PNRF_IMG_U8), pix_stride 3 or 4 values per pixel of which the first three
+ * are taken (an [H,W,3] image as loaded, no permute) -> the view's texels (r, g, b, 0).  uint8 -> fp32 is one correctly rounded fp32 division k / 255:
+ * the 256 values of (k / 255.).astype(float32), what load_llff produces (load_llff.py).  A PNRF_SCENE_U8 cache takes uint8 images only — an fp32 image
+ * is refused (PNRF_E_ARG), never quantised silently.  pose_host: HOST [3,4] camera-to-world, 12 finite floats; it travels in the ingest kernel's
+ * arguments, so both the image and the pose are read in stream order and the host buffer is free when the call returns.  Arguments are checked
+ * before any device work. */
+int pnrf_scene_set_view(pnrf_scene_t* s, int v, const void* img, int img_dtype, int pix_stride, const float* pose_host, void* stream);
+/* The driver's K (target camera: rays) and ref_K (source cameras: projection), HOST [3,3] each, finite.  Synchronous copy; configuration. */
+int pnrf_scene_set_intrinsics(pnrf_scene_t* s, const float* K_target_host, const float* K_ref_host);
+/* Neighbour selection for the target pose c2w dev [3,4] (run_S_eS_eN_alter_trt.py:281-296), two launches:
+ *   ranking     d_v = sqrt((dx dx + dy dy) + dz dz) of the camera centres in fp32, every operation rounded once; stable ascending rank (ties to the
+ *               lower index, NaN last: np.argsort(kind='stable')); ref_nos_out dev int32 [nb] = the nb nearest views — pronerf_amd.render.select_neighbors
+ *               index for index.  One workgroup ranks by counting over the distances in LDS (O(nv^2) comparisons: microseconds for tens of views).
+ *   projection  proj_out dev [nb,3,4], proj[k] = K_ref . diag(1,-1,-1) . pose[ref_nos[k]]: the fp32 x fp32 products are exact in fp64, each three-term sum
+ *               is formed left to right in fp64 and rounded once to fp32 — independent of FMA contraction, reproducible with element-wise float64
+ *               numpy.  NOT the bits of an fp32 matmul (render.projection_matrices): both lie within 4 x 2^-24 (|K| . |diag . pose|) of the exact product.
+ *   gather      img4_out dev [nb,Hf,Wf,4] (16-byte aligned), img4_out[k] = float4(cache[ref_nos[k]]): what pnrf_images_pack makes of the selected images,
+ *               bit for bit; ref_nos is read from device memory.
+ * nb 1 .. 8, at most nv (PNRF_E_ARG); every view and the intrinsics must have been set (PNRF_E_STATE). */
+int pnrf_scene_select_fwd(const pnrf_scene_t* s, const float* c2w_dev, int nb, int32_t* ref_nos_out, float* proj_out, float* img4_out, void* stream);
+/* pnrf_frame_rays_blocks_fwd with the camera in device memory: K_dev dev [3,3], c2w_dev dev [3,4].  Same per-pixel code (csrc/pnrf_frame_rays.h), the
+ * double-precision NDC scale evaluated on the device: output bit-identical to the host-pointer entry point. */
+int pnrf_frame_rays_dev_fwd(const float* K_dev, const float* c2w_dev, int H, int W, float near, float far, float or_near, float or_far,
+                            int64_t first, int64_t block, int64_t stride, int64_t count, float* rays, float* or_rays, void* stream);
+/* Pose -> rows of the frame on one stream: pnrf_scene_select_fwd, pnrf_frame_rays_dev_fwd with the scene's K_target, pnrf_render_rays_fwd — three
+ * launches (select, gather, rays) in front of that call's own, nothing allocated, nothing read back.  rgbd dev [count,4], sort_idx optional; first / block / stride / count as
+ * pnrf_frame_rays_blocks_fwd (a whole frame: 0, H W, 0, H W); count <= the context's max_rays.  ws: dev, 16-byte aligned, ws_bytes >=
+ * pnrf_render_pose_workspace_bytes(scene, nb, count) — it holds ref_nos, proj, img4, rays and or_rays of the call; contents irrelevant, concurrent calls
+ * need separate workspaces (and contexts). */
+int pnrf_render_pose_workspace_bytes(const pnrf_scene_t* s, int nb, int64_t max_rays, int64_t* bytes);
+int pnrf_render_pose_fwd(pnrf_ctx_t* ctx, const pnrf_scene_t* s, const float* c2w_dev, int nb, int H, int W, float near, float far, float or_near,
+                         float or_far, int64_t first, int64_t block, int64_t stride, int64_t count, float eps, void* ws, int64_t ws_bytes,
+                         float* rgbd, int64_t* sort_idx, void* stream);
 
 /* Host helper: torch.linspace(start,end,n) in fp32, as used for the 48 ray points
  * (run_S_eS_eN_alter_trt.py:556-557).  out: HOST [n]. */

@@ -73,6 +73,15 @@ SIGNATURES = {
     'pnrf_image_metrics_workspace_bytes': (_i64, [_i, _i, _i]),
     'pnrf_image_metrics_fwd': (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _p, _p, _p, _i64, _p]),
     'pnrf_frame_to8b_fwd': (_i, [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p]),
+    # device-resident scene: pose -> frame
+    'pnrf_scene_create': (_i, [_i, _i, _i, _i, C.POINTER(_p)]),
+    'pnrf_scene_free': (_i, [_p]),
+    'pnrf_scene_set_view': (_i, [_p, _i, _p, _i, _i, C.POINTER(_f), _p]),
+    'pnrf_scene_set_intrinsics': (_i, [_p, C.POINTER(_f), C.POINTER(_f)]),
+    'pnrf_scene_select_fwd': (_i, [_p, _p, _i, _p, _p, _p, _p]),
+    'pnrf_frame_rays_dev_fwd': (_i, [_p, _p, _i, _i, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    'pnrf_render_pose_workspace_bytes': (_i, [_p, _i, _i64, C.POINTER(_i64)]),
+    'pnrf_render_pose_fwd': (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _f, _p, _i64, _p, _p, _p]),
     # stage-2 training step
     'pnrf_composite_bwd': (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
     'pnrf_posenc_bwd': (_i, [_p, _p, _p, _i64, _i, _p]),

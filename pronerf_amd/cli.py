@@ -62,6 +62,8 @@ def infer_argv(ns):
         argv += ['--metrics', ns.metrics]
     if getattr(ns, 'device_to8b', False):
         argv.append('--device_to8b')
+    if getattr(ns, 'scene_cache', None) is not None:
+        argv += ['--scene_cache', ns.scene_cache]
     return argv + _extra(ns)
 
 
@@ -113,6 +115,8 @@ def build_parser():
     def frame_tail(q):
         q.add_argument('--metrics', choices=['psnr', 'psnr,ssim'], default=None, help="'psnr,ssim': PSNR and SSIM of the rendered test views, taken on the device")
         q.add_argument('--device_to8b', '--device-to8b', action='store_true', dest='device_to8b', help='8-bit PNG planes converted on the device')
+        q.add_argument('--scene_cache', '--scene-cache', choices=['f32', 'u8'], default=None, dest='scene_cache',
+                       help="source views resident on the device, every pose rendered from its twelve floats ('u8': RGBA8 texels)")
 
     q = sub.add_parser('train-stage1', help='alternating sampler / NeRF training')
     q.add_argument('--config', default='configs/llff/fern/fern_epi.txt')

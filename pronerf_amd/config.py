@@ -40,7 +40,10 @@ _VARIANT = {
             ('pnrf_preset', str, 'default'),
             # not in the reference: 'psnr,ssim' takes PSNR and SSIM of the hold-out views on the device (render_path's pnrf_metrics); device_to8b hands
             # the PNG writer 8-bit planes converted on the device (pnrf_device_to8b)
-            ('metrics', str, 'psnr'), ('device_to8b', 'flag', False)],
+            ('metrics', str, 'psnr'), ('device_to8b', 'flag', False),
+            # not in the reference: 'f32' | 'u8' keeps the source views on the device and renders every pose from its twelve floats (render_path's
+            # pnrf_scene_cache; 'u8': RGBA8 texels, for images that are exact 8-bit values)
+            ('scene_cache', str, None)],
     # stage 2 (run_S_eS_eN_alter_base_refine2.py)
     'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)],
     # stage 1 (run_S_eS_eN_alter_base.py)

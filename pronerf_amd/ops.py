@@ -185,6 +185,26 @@ def frame_rays(K, c2w, H, W, near=0.0, far=1.0, or_near=1.0, or_far=10.0, first=
     return rays, orr
 
 
+def _dev_mat(t, name, shape):
+    """A contiguous fp32 GPU tensor of exactly ``shape`` (a camera matrix in device memory), used in place."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != f32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise PnrfError(f'{name}: expected a contiguous float32 GPU tensor {list(shape)}, got {getattr(t, "dtype", type(t))} '
+                        f'{tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
+    return t
+
+
+def frame_rays_dev(K, c2w, H, W, near=0.0, far=1.0, or_near=1.0, or_far=10.0, first=0, count=None, block=None, stride=0):
+    """``frame_rays`` with the camera in device memory (pnrf_frame_rays_dev_fwd): K [3,3] and c2w [3,4] are GPU tensors read by the kernel in stream
+    order — no host copy, no synchronisation; bit-identical rows."""
+    K = _dev_mat(K, 'K', (3, 3)); c2w = _dev_mat(c2w, 'c2w', (3, 4))
+    count = H * W - first if count is None else count
+    rays = torch.empty(count, 11, device=c2w.device, dtype=f32)
+    orr = torch.empty(count, 11, device=c2w.device, dtype=f32)
+    check(_lib.load().pnrf_frame_rays_dev_fwd(_ptr(K), _ptr(c2w), H, W, near, far, or_near, or_far, first, int(max(count, 1) if block is None else block),
+                                              int(0 if block is None else stride), count, _ptr(rays), _ptr(orr), _stream()), 'pnrf_frame_rays_dev_fwd')
+    return rays, orr
+
+
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
     rays_o = _chk(rays_o, 'rays_o', (3,)); rays_d = _chk(rays_d, 'rays_d', (3,))
     lead = rays_o.shape
@@ -438,6 +458,115 @@ class RenderContext:
         check(_lib.load().pnrf_render_rays_fwd(self.handle, _ptr(rays), _ptr(or_rays), _ptr(img4), _ptr(proj), nb, Hf, Wf, eps,
                                                _ptr(rgbd), _ptr(idx), n, _stream()), 'pnrf_render_rays_fwd')
         return rgbd, idx
+
+    def render_pose(self, scene, c2w, nb, H, W, near=0.0, far=1.0, or_near=1.0, or_far=10.0, first=0, count=None, block=None, stride=0, eps=1e-5,
+                    ws=None, out=None, want_idx=False):
+        """Pose -> rows of the frame (pnrf_render_pose_fwd): neighbour selection, gather, rays and render_rays on the current stream from the GPU
+        tensor c2w [3,4], read in place.  ws: uint8 GPU tensor of ``scene.pose_workspace_bytes(nb, count)`` bytes (None: allocated here)."""
+        c2w = _dev_mat(c2w, 'c2w', (3, 4))
+        n = H * W - first if count is None else int(count)
+        need = scene.pose_workspace_bytes(nb, n)
+        if ws is None:
+            ws = torch.empty(need, device=c2w.device, dtype=torch.uint8)
+        elif not isinstance(ws, torch.Tensor) or ws.device != c2w.device or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+            raise PnrfError(f'render_pose: ws must be a contiguous uint8 tensor of at least {need} bytes on {c2w.device}')
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.device != c2w.device or out.dtype != f32 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+                raise PnrfError(f'render_pose: out must be a contiguous float32 tensor [{n}, 4] on {c2w.device}')
+        rgbd = out if out is not None else torch.empty(n, 4, device=c2w.device, dtype=f32)
+        idx = torch.empty(n, 8, device=c2w.device, dtype=torch.int64) if want_idx else None
+        check(_lib.load().pnrf_render_pose_fwd(self.handle, scene.handle, _ptr(c2w), int(nb), int(H), int(W), near, far, or_near, or_far, int(first),
+                                               int(max(n, 1) if block is None else block), int(0 if block is None else stride), n, eps, _ptr(ws), ws.numel(),
+                                               _ptr(rgbd), _ptr(idx), _stream()), 'pnrf_render_pose_fwd')
+        return rgbd, idx
+
+
+class Scene:
+    """pnrf_scene: the source views of a scene on the device — texel cache [nv,Hf,Wf,4], poses, intrinsics — uploaded once; ``select`` and
+    ``RenderContext.render_pose`` derive everything a target pose needs from it on the device.
+
+    cache: 'f32' (float4 texels, exact for any image) or 'u8' (RGBA8 texels, a quarter of the memory; uint8 images only)."""
+
+    FORMATS = {'f32': 0, 'u8': 1}
+
+    def __init__(self, nv, Hf, Wf, cache='f32', device='cuda:0'):
+        if cache not in self.FORMATS:
+            raise PnrfError(f"Scene: cache must be 'f32' or 'u8', got {cache!r}")
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise PnrfError('Scene needs a GPU device (pronerf_amd has no CPU path)')
+        h = C.c_void_p()
+        check(_lib.load().pnrf_scene_create(int(nv), int(Hf), int(Wf), self.FORMATS[cache], C.byref(h)), 'pnrf_scene_create')
+        self.handle = h
+        self.nv, self.Hf, self.Wf, self.cache = int(nv), int(Hf), int(Wf), cache
+        self.K = None                                      # device copy of the target intrinsics (what frame_rays_dev takes)
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None):
+                _lib.load().pnrf_scene_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def set_view(self, v, image, pose):
+        """image: [Hf,Wf,3|4] float32 or uint8, numpy or torch (host data is copied to the device first; a GPU tensor is read in place);
+        pose: host [3,4] camera-to-world."""
+        img = torch.as_tensor(image)
+        if img.dtype not in (torch.float32, torch.uint8):
+            if img.dtype.is_floating_point:
+                img = img.to(torch.float32)
+            else:
+                raise PnrfError(f'Scene.set_view: images must be float32 or uint8, got {img.dtype}')
+        if img.dim() != 3 or tuple(img.shape[:2]) != (self.Hf, self.Wf) or img.shape[2] not in (3, 4):
+            raise PnrfError(f'Scene.set_view: expected an image [{self.Hf}, {self.Wf}, 3|4], got {tuple(img.shape)}')
+        img = img.to(self.device).contiguous()
+        ph = np.ascontiguousarray(np.asarray(pose.detach().cpu() if isinstance(pose, torch.Tensor) else pose, dtype=np.float32)[:3, :4])
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_scene_set_view(self.handle, int(v), _ptr(img), 1 if img.dtype == torch.uint8 else 0, int(img.shape[2]),
+                                                  ph.ctypes.data_as(C.POINTER(C.c_float)), _stream()), 'pnrf_scene_set_view')
+            img.record_stream(torch.cuda.current_stream())
+        return self
+
+    def set_intrinsics(self, K, ref_K=None):
+        fp = C.POINTER(C.c_float)
+        host = lambda m: np.ascontiguousarray(np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float32).reshape(3, 3))
+        Kh = host(K)
+        Rh = Kh if ref_K is None else host(ref_K)
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_scene_set_intrinsics(self.handle, Kh.ctypes.data_as(fp), Rh.ctypes.data_as(fp)), 'pnrf_scene_set_intrinsics')
+        self.K = torch.from_numpy(Kh).to(self.device)
+        return self
+
+    @classmethod
+    def from_views(cls, poses, images, K, ref_K=None, cache='f32', device='cuda:0'):
+        """poses [nv,3,4]; images [nv,Hf,Wf,3] numpy or torch, float32 or uint8 (one view at a time travels to the device); K, ref_K: the driver's
+        target / source intrinsics (ref_K None: K)."""
+        nv, Hf, Wf = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+        if len(poses) != nv:
+            raise PnrfError(f'Scene.from_views: {nv} images but {len(poses)} poses')
+        self = cls(nv, Hf, Wf, cache=cache, device=device)
+        self.set_intrinsics(K, ref_K)
+        for v in range(nv):
+            self.set_view(v, images[v], poses[v])
+        return self
+
+    def select(self, c2w, nb):
+        """Neighbours of the target pose c2w (GPU tensor [3,4], read in place) -> (ref_nos int32 [nb], proj [nb,3,4], img4 [nb,Hf,Wf,4])
+        (pnrf_scene_select_fwd)."""
+        c2w = _dev_mat(c2w, 'c2w', (3, 4))
+        nb = int(nb)
+        with torch.cuda.device(self.device):
+            ref = torch.empty(max(nb, 0), device=self.device, dtype=torch.int32)
+            proj = torch.empty(max(nb, 0), 3, 4, device=self.device, dtype=f32)
+            img4 = torch.empty(max(nb, 0), self.Hf, self.Wf, 4, device=self.device, dtype=f32)
+            check(_lib.load().pnrf_scene_select_fwd(self.handle, _ptr(c2w), nb, _ptr(ref), _ptr(proj), _ptr(img4), _stream()), 'pnrf_scene_select_fwd')
+        return ref, proj, img4
+
+    def pose_workspace_bytes(self, nb, max_rays):
+        v = C.c_int64()
+        check(_lib.load().pnrf_render_pose_workspace_bytes(self.handle, int(nb), int(max_rays), C.byref(v)), 'pnrf_render_pose_workspace_bytes')
+        return int(v.value)
 
 
 def linspace(start, end, n):

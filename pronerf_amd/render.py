@@ -156,6 +156,9 @@ class Renderer:
         self.img4 = None
         self.proj = None
         self.ref_nos = None
+        self.scene = None                # set_scene(): the device-resident source views of render_pose
+        self._pose = None                # [3,4] device buffer a host pose is copied into
+        self._pose_ws = None             # workspace of render_pose (neighbour texels, matrices, rays), grown on demand
 
     # ---- engine files (the reference's <export_dir>/*_fp16.trt, pronerf/tensorrt.py:8-14)
     ENGINE_FILES = {'nerf': 'nerf.pnrf', 'sampler': 'minmaxrays_net.pnrf', 'refine': 'refine_net.pnrf'}
@@ -216,6 +219,84 @@ class Renderer:
             raise ops.PnrfError('Renderer.render_rays: call set_views() first')
         with torch.cuda.device(self.device):
             return self.ctx.render_rays(rays, or_rays, self.img4, self.proj, eps=eps, want_idx=want_idx, out=out)
+
+
+    # ---- pose -> frame from a device-resident scene (nothing of the per-pose set-up on the host)
+    def set_scene(self, poses, images, K, ref_K=None, cache='f32'):
+        """Upload the scene's source views once (``ops.Scene.from_views``): poses [nv,3,4], images [nv,Hf,Wf,3] float32 or uint8, K / ref_K the
+        target / source intrinsics.  cache 'u8' keeps RGBA8 texels (uint8 images only).  Also accepts a ready ``ops.Scene`` as ``poses``."""
+        if isinstance(poses, ops.Scene):
+            if poses.device != self.device:
+                raise ops.PnrfError(f'Renderer.set_scene: the scene lives on {poses.device}, the renderer on {self.device}')
+            self.scene = poses
+        else:
+            self.scene = ops.Scene.from_views(poses, images, K, ref_K, cache=cache, device=self.device)
+        if self.scene.nv < self.num_neighbor:
+            raise ops.PnrfError(f'Renderer.set_scene: the refine net takes {self.num_neighbor} neighbour views, the scene has {self.scene.nv}')
+        return self.scene
+
+    def _pose_workspace(self, n):
+        need = self.scene.pose_workspace_bytes(self.num_neighbor, n)
+        if self._pose_ws is None or self._pose_ws.numel() < need:
+            self._pose_ws = None                                   # free before the larger one is allocated
+            self._pose_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return self._pose_ws
+
+    def render_pose(self, c2w, H, W, near=0., far=1., or_near=1., or_far=10., out=None, first=0, count=None, block=None, stride=0, eps=1e-5):
+        """rgbd [count,4] of the frame seen from ``c2w`` — neighbour selection, projection matrices, neighbour texels, rays and the three fused stages
+        as kernels on the current stream.  c2w: a float32 GPU tensor [3,4] is used in place, with no synchronisation (change its contents and call
+        again, or replay a captured graph); host data is copied into a small device buffer of the renderer first.  first / count / block / stride:
+        the rows of a ray partition (``RayPartition.frame_rays_args``)."""
+        if self.scene is None:
+            raise ops.PnrfError('Renderer.render_pose: call set_scene() first')
+        with torch.cuda.device(self.device):
+            if not (isinstance(c2w, torch.Tensor) and c2w.is_cuda):
+                if self._pose is None:
+                    self._pose = torch.empty(3, 4, device=self.device, dtype=torch.float32)
+                self._pose.copy_(torch.as_tensor(np.asarray(c2w.detach() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)[:3, :4].copy()))
+                c2w = self._pose
+            n = H * W - first if count is None else int(count)
+            rgbd, _ = self.ctx.render_pose(self.scene, c2w, self.num_neighbor, H, W, near=near, far=far, or_near=or_near, or_far=or_far, first=first,
+                                           count=n, block=block, stride=stride, eps=eps, ws=self._pose_workspace(n), out=out)
+        return rgbd
+
+    def capture_pose(self, H, W, **kwargs):
+        """One hipGraph of ``render_pose(c2w, H, W, **kwargs)``: ``PoseGraph.replay(c2w)`` writes the pose into the graph's device buffer and replays it."""
+        return PoseGraph(self, H, W, **kwargs)
+
+
+class PoseGraph:
+    """``Renderer.render_pose`` captured once (``torch.cuda.graph``; a single stream, so a linear graph): per pose, twelve floats go into the static
+    ``c2w`` buffer and the graph is replayed.  ``rgbd`` is the static output tensor every replay writes."""
+
+    def __init__(self, renderer, H, W, **kwargs):
+        if 'out' in kwargs:
+            raise ops.PnrfError('capture_pose: the graph owns its output tensor (PoseGraph.rgbd)')
+        self.renderer = renderer
+        dev = renderer.device
+        n = H * W - kwargs.get('first', 0) if kwargs.get('count') is None else int(kwargs['count'])
+        with torch.cuda.device(dev):
+            self.c2w = torch.eye(3, 4, device=dev, dtype=torch.float32)
+            self.rgbd = torch.empty(n, 4, device=dev, dtype=torch.float32)
+            side = torch.cuda.Stream(device=dev)                    # one eager call first: the workspace is allocated outside the capture
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                renderer.render_pose(self.c2w, H, W, out=self.rgbd, **kwargs)
+            torch.cuda.current_stream().wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                renderer.render_pose(self.c2w, H, W, out=self.rgbd, **kwargs)
+            self._ws = renderer._pose_ws                            # the buffers the graph's kernels address stay alive with it
+            self._scene = renderer.scene
+
+    def replay(self, c2w):
+        """c2w: [3,4] host data or tensor on any device -> the static rgbd tensor (valid until the next replay)."""
+        if isinstance(c2w, torch.Tensor):
+            self.c2w.copy_(c2w[:3, :4].to(torch.float32), non_blocking=True)
+        else:
+            self.c2w.copy_(torch.as_tensor(np.asarray(c2w, dtype=np.float32)[:3, :4].copy()))
+        self.graph.replay()
+        return self.rgbd
 
 
 class ChunkedRenderer:
