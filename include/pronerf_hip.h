@@ -325,6 +325,27 @@ int pnrf_ctx_sampler_stats(pnrf_ctx_t* ctx, int64_t* rays_second_pass);
  * third pass) in the context's most recent pnrf_render_rays_fwd: 0 for every net whose activations stay below 65 504 / log2(e) (waits for the
  * device; diagnostics). */
 int pnrf_ctx_sampler_saturated(pnrf_ctx_t* ctx, int64_t* rays_third_pass);
+/* NeRF stage of pnrf_render_rays_fwd: evaluate only the samples whose sampler gate is open.  Compositing multiplies a sample's alpha by relu(mul), and mul
+ * is an output of the sampler: where mul <= 0 (or NaN) the sample's weight is exactly 0 and the network's answer for it cannot change the output, as long as
+ * that answer is finite.  On this path a small kernel lists the live columns (ray * 8 + s with mul > 0) and decides on the device: if at least
+ * PNRF_NERF_SKIP_DEAD_PERCENT percent of the call's samples are dead, the MLP runs over the compacted list and a compositing pass follows (LIST); otherwise the
+ * fused kernel runs as ever (DENSE).  rgbd is the same bit for bit either way; the host reads nothing back and the call still captures into a graph.  The
+ * path's workspace, 160 bytes per ray of max_rays, is allocated by pnrf_ctx_set_nerf_skip or by the context's first call on the path outside a stream capture;
+ * a call inside a capture that finds none, and a call of 2^28 rays or more (the list holds int32 column ids), run the fused kernel alone.
+ *   PNRF_NERF_SKIP_NEVER   the fused kernel alone, no extra launch
+ *   PNRF_NERF_SKIP_AUTO    (a new context) that path for calls of more than PNRF_NERF_SKIP_MIN_RAYS rays — one wide NeRF batch per CU on 256 CUs; below that
+ *                          a call's time is the latency of one batch and two more launches would only add to it
+ *   PNRF_NERF_SKIP_ALWAYS  that path and LIST whatever the call size or the dead share (tests, A/B timing)
+ * Handles on PNRF_VARIANT_NERF_4X64 / PNRF_VARIANT_BF16_32X32 always run the fused kernel alone. */
+#define PNRF_NERF_SKIP_NEVER 0
+#define PNRF_NERF_SKIP_AUTO 1
+#define PNRF_NERF_SKIP_ALWAYS 2
+#define PNRF_NERF_SKIP_MIN_RAYS 8192
+#define PNRF_NERF_SKIP_DEAD_PERCENT 2      /* break-even, measured: (list builder 0.019 + compositing pass 0.031 + empty launch 0.005 ms) / dense stage 3.29 ms = 1.7 %, rounded up; DESIGN 4.10 */
+int pnrf_ctx_set_nerf_skip(pnrf_ctx_t* ctx, int mode);
+/* The most recent pnrf_render_rays_fwd of the context: live columns the builder counted (-1 if the call did not take that path) and whether it chose
+ * LIST (1) or DENSE (0) (waits for the device; diagnostics). */
+int pnrf_ctx_nerf_live(pnrf_ctx_t* ctx, int64_t* live_columns, int* list_mode);
 /* Per-stage device time of pnrf_render_rays_fwd (what the reference gets from line_profiler / the cuda events around
  * render(), run_S_eS_eN_alter_trt.py:327-332, at frame granularity): after _begin, the next max_frames calls on this
  * context record an event before and after each of the three kernels on the caller's stream; _end waits for the last

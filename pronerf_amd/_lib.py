@@ -66,6 +66,8 @@ SIGNATURES = {
     'pnrf_ctx_set_sampler_kappa': (_i, [_p, _f]),
     'pnrf_ctx_get_sampler_kappa': (_i, [_p, C.POINTER(_f)]),
     'pnrf_ctx_sampler_saturated': (_i, [_p, C.POINTER(_i64)]),
+    'pnrf_ctx_set_nerf_skip': (_i, [_p, _i]),
+    'pnrf_ctx_nerf_live': (_i, [_p, C.POINTER(_i64), C.POINTER(_i)]),
     'pnrf_ctx_profile_begin': (_i, [_p, _i]),
     'pnrf_ctx_profile_end': (_i, [_p, C.POINTER(C.c_float), C.POINTER(_i)]),
     'pnrf_linspace': (_i, [_f, _f, _i, C.POINTER(_f)]),

@@ -88,3 +88,8 @@ int pnrf_sampler_fwd_ws_impl(const pnrf_mlp_t* h, const float* rays, int64_t n, 
 int pnrf_nerf_fwd_queue_impl(const pnrf_mlp_t* h, const float* pts, const float* rays, const float* z, const float* add_sorted,
                              const float* mul_sorted, const float* noise, float clampv, int white_bkgd, int S, float* rgbd, float* raw,
                              int64_t n, int* queue, void* stream);
+// ... and with the compacted-column path (skip != NULL): live-list builder, dense kernel, list kernel, compositing pass; see pnrf_mlp_kernels.hip
+int pnrf_nerf_fwd_skip_impl(const pnrf_mlp_t* h, const float* pts, const float* rays, const float* z, const float* add_sorted,
+                            const float* mul_sorted, const float* noise, float clampv, int white_bkgd, int S, float* rgbd, float* raw,
+                            int64_t n, int* queue, int* skip, int* list, int force_list, void* stream);
+bool pnrf_nerf_skip_supported(const pnrf_mlp_t* h);

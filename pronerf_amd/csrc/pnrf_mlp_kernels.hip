@@ -1436,7 +1436,12 @@ struct NerfArgs {
   float clampv; int S;                                               // raw clamp (stage 1: 10), samples per ray (8; stage-1 exploration: 8..256)
   float* y; const int* outmap;                      // module-level consumer
   int* queue;                                       // nerf16_kernel: [0] batches handed out beyond the first round, [1] workgroups done; NULL = static stride
+  const int* list; int* skip;                       // compacted-column path (nerf_live_list_kernel): live column ids; skip[SKIP_*] words.  NULL = plain dense call
 };
+// Words of a context's live-column state (skip[]: words 10 .. 13 of the sampler workspace's header).  RUN and DONE are zero between launches (the last
+// workgroup of the builder puts them back); LIVE and MODE hold the most recent call's result until the next builder overwrites them.
+enum { SKIP_RUN = 0, SKIP_DONE = 1, SKIP_LIVE = 2, SKIP_MODE = 3 };
+enum { SKIP_MODE_DENSE = 0, SKIP_MODE_LIST = 1 };
 
 // sin / cos of scale * x, scale a power of two: hardware v_sin / v_cos on the fraction of the angle in revolutions (valid for any
 // magnitude; error of the fraction 2^-24 * |scale x / 2 pi|, far below the bf16 rounding of the MLP input)
@@ -1720,6 +1725,45 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void nerf_kernel(NerfArg
   st.drain();
 }
 
+// Compositing of one ray's 8 samples held in 8 adjacent lanes (lane & 7 = s), results in all 8: the arithmetic of nerf16_kernel's fused epilogue and of
+// nerf_composite_kernel (the compacted-column path), one body for both — their outputs are bit-identical by construction.  Every lane of the wave calls it.
+__device__ __forceinline__ float ray_dir_norm(const float* ry) {
+  return ieee_sqrt(ieee_add(ieee_add(ieee_mul(ry[3], ry[3]), ieee_mul(ry[4], ry[4])), ieee_mul(ry[5], ry[5])));
+}
+__device__ __forceinline__ float4 composite8_dpp(const NerfArgs& a, float r0, float r1, float r2, float r3, float dn, float zc, float ad, float mu, float noise, int s) {
+  if (a.clampv > 0.f) {                                                         // base.py:523
+    r0 = fminf(fmaxf(r0, -a.clampv), a.clampv); r1 = fminf(fmaxf(r1, -a.clampv), a.clampv);
+    r2 = fminf(fmaxf(r2, -a.clampv), a.clampv); r3 = fminf(fmaxf(r3, -a.clampv), a.clampv);
+  }
+  // the 8 samples of a ray sit in 8 adjacent lanes: neighbour, exclusive product and the sums go through DPP lane moves
+  // (row_shl / row_shr / quad_perm / row_half_mirror) instead of LDS permutes; tree order instead of torch's left-to-right order,
+  // a difference of fp32 round-off under a bf16-grade network output
+  const float znext = dpp_mov<0x101>(zc);                                       // row_shl:1
+  float dist = (s < 7) ? ieee_sub(znext, zc) : 1e10f;                          // trt.py:579-581
+  dist = ieee_mul(dist, dn);                                                   // :583
+  const float cr = sigmoid_fast(r0), cg = sigmoid_fast(r1), cbv = sigmoid_fast(r2);   // :585
+  const float sg = fmaxf(ieee_add(a.noise ? ieee_add(r3, noise) : r3, ad), 0.f);     // refine2.py:508
+  float alpha = ieee_sub(1.f, __expf(ieee_mul(-sg, dist)));                   // :577,587
+  if (a.mul) alpha = ieee_mul(alpha, fmaxf(mu, 0.f));                          // :588
+  const float xk = ieee_add(ieee_sub(1.f, alpha), 1e-10f);                    // :590
+  // exclusive cumprod: shift by one (row_shr:1), then scan.  Every lane move is executed by all lanes and selected afterwards: under
+  // a branch the lanes switched off would read as zero in their neighbours' moves
+  const float xprev = dpp_mov<0x111>(xk);
+  float T = s >= 1 ? xprev : 1.f;
+  { const float t = dpp_mov<0x111>(T); T = ieee_mul(T, s >= 1 ? t : 1.f); }
+  { const float t = dpp_mov<0x112>(T); T = ieee_mul(T, s >= 2 ? t : 1.f); }
+  { const float t = dpp_mov<0x114>(T); T = ieee_mul(T, s >= 4 ? t : 1.f); }
+  const float wgt = ieee_mul(alpha, T);
+  float s0 = sum8_dpp(ieee_mul(wgt, cr)), s1 = sum8_dpp(ieee_mul(wgt, cg)), s2 = sum8_dpp(ieee_mul(wgt, cbv));    // :591 sum over samples
+  const float s3 = sum8_dpp(ieee_mul(wgt, zc));                                // :593 depth_map
+  const float sa = a.white_bkgd ? sum8_dpp(wgt) : 0.f;                          // acc_map
+  if (a.white_bkgd) {                                                           // refine2.py:519-520
+    const float bg = ieee_sub(1.f, sa);
+    s0 = ieee_add(s0, bg); s1 = ieee_add(s1, bg); s2 = ieee_add(s2, bg);
+  }
+  return make_float4(s0, s1, s2, s3);
+}
+
 // ------------------------------------------------------------------------------------------ DoNeRFTRT on the 16x16x32 engine
 // nerf16_kernel: the fused NeRF stage (positional encoding -> 8-layer MLP -> compositing) on layer_b16.  Per wave two blocks of
 // 16 columns (ray samples), 8 waves = 256 columns per workgroup batch, like nerf_kernel<1, 8>.  Lane l: column l&15 of each block,
@@ -1763,11 +1807,23 @@ struct HiddenEpi16 {
 // NCB = 2: 8 waves of 32 columns, two waves per SIMD (the default).  NCB = 4: 4 waves of 64 columns, one wave per SIMD: every weight fragment read
 // from LDS feeds four MFMAs instead of two (tools/lds_mfma_probe.hip: 1.57 -> 1.81 PFLOP/s for the bare hidden-layer loop).
 // NW: waves per workgroup.  16 / NCB (the default); NCB = 2, NW = 4: 128 rows per batch, a SIMD per wave (as sampler_h16_kernel<4>).
-template <bool CLS, int NCB = 2, class P = PrecBf16, int NW = 16 / NCB>
-__global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfArgs a) {
+// LIST (nerf16_list_kernel, the compacted-column path of a context's large calls): column c of batch b is sample list[c] of the frame — the live columns
+// (mul > 0) that nerf_live_list_kernel collected —, the batch count comes from the device's live count, the raw network output goes to raw[list[c]] and
+// nerf_composite_kernel composites behind it.  The dense kernel of such a call leaves at once when the mode word says LIST, the list kernel when it says DENSE.
+template <bool CLS, int NCB, class P, int NW, bool LIST>
+__device__ __forceinline__ void nerf16_body(const NerfArgs& a) {
   constexpr int TPB = 64 * NW;
   using Epi = HiddenEpi16<NCB, P>;
   using v8 = typename P::v8;
+  if (a.skip && a.skip[SKIP_MODE] != (LIST ? SKIP_MODE_LIST : SKIP_MODE_DENSE)) return;
+  const int nlive = LIST ? a.skip[SKIP_LIVE] : 0;
+  const int nbatch = LIST ? (nlive + NW * 16 * NCB - 1) / (NW * 16 * NCB) : a.nbatch;
+  if constexpr (LIST) {
+    if ((int)blockIdx.x >= nbatch) {             // fewer live batches than workgroups: nothing to do but to be counted (the queue's re-arm below)
+      if (threadIdx.x == 0 && atomicAdd(a.queue + 1, 1) == (int)gridDim.x - 1) { a.queue[0] = 0; a.queue[1] = 0; }
+      return;
+    }
+  }
   P::enter();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* bias_lds = (float*)(smem + RING_BYTES);
@@ -1791,7 +1847,7 @@ __global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfA
   young_half_priority<NW>();
   const char* ringlane = smem + lane * 16;
   const float* biaslane = bias_lds + 4 * g;
-  const bool composite = a.S == 8 && a.rgbd;
+  const bool composite = !LIST && a.S == 8 && a.rgbd;
 
   // Batch hand-out.  Without a queue (operator-level calls): the static stride.  With one (a context's calls): a workgroup's first batch is its
   // static one, every further one comes from an atomic counter — a workgroup that starts late because another stream's kernel held its CU (a
@@ -1799,7 +1855,7 @@ __global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfA
   // batches after everybody else has finished.  The counter is fetched at the top of a batch and consumed at its end (its latency is hidden);
   // the last workgroup to leave puts the two words back to zero for the next launch on this context.
   __shared__ __attribute__((aligned(16))) int s_next[4];
-  for (int batch = blockIdx.x; batch < a.nbatch;) {
+  for (int batch = blockIdx.x; batch < nbatch;) {
     int q_pend = 0;
     if (a.queue && threadIdx.x == 0) q_pend = atomicAdd(a.queue, 1);
     int64_t row[NCB];
@@ -1809,14 +1865,18 @@ __global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfA
     static_for<NCB>([&](auto cbc) {
       constexpr int cb = decltype(cbc)::value;
       row[cb] = (int64_t)batch * (NW * 16 * NCB) + wave * (16 * NCB) + cb * 16 + c16;
-      valid[cb] = row[cb] < nrows;
-      const int64_t rr = valid[cb] ? row[cb] : nrows - 1;
+      valid[cb] = row[cb] < (LIST ? (int64_t)nlive : nrows);
+      int64_t rr = valid[cb] ? row[cb] : nrows - 1;
+      if constexpr (LIST) {                       // (nlive >= 1 here: this workgroup has a batch)
+        rr = a.list[valid[cb] ? row[cb] : (int64_t)nlive - 1];
+        row[cb] = rr;                             // where the column's raw output goes
+      }
       const float* pp = a.pts + rr * 3;
       const float* ry = a.rays + (a.S == 8 ? (rr >> 3) : rr / a.S) * 11;
       const float x3[3] = {pp[0], pp[1], pp[2]};
       const float v3[3] = {ry[8], ry[9], ry[10]};
       if (composite) {
-        e_dn[cb] = ieee_sqrt(ieee_add(ieee_add(ieee_mul(ry[3], ry[3]), ieee_mul(ry[4], ry[4])), ieee_mul(ry[5], ry[5])));
+        e_dn[cb] = ray_dir_norm(ry);
         e_z[cb] = a.z[rr]; e_add[cb] = a.add ? a.add[rr] : 0.f; e_mul[cb] = a.mul ? a.mul[rr] : 1.f;
         e_noise[cb] = a.noise ? a.noise[rr] : 0.f;
       }
@@ -1934,37 +1994,8 @@ __global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfA
       if (!composite) return;
       const int64_t ray = rr >> 3;
       const int s = (int)(rr & 7);
-      const float dn = e_dn[cb], zc = e_z[cb], ad = e_add[cb], mu = e_mul[cb];
-      if (a.clampv > 0.f) {                                                         // base.py:523
-        r0 = fminf(fmaxf(r0, -a.clampv), a.clampv); r1 = fminf(fmaxf(r1, -a.clampv), a.clampv);
-        r2 = fminf(fmaxf(r2, -a.clampv), a.clampv); r3 = fminf(fmaxf(r3, -a.clampv), a.clampv);
-      }
-      // the 8 samples of a ray sit in 8 adjacent lanes: neighbour, exclusive product and the sums go through DPP lane moves
-      // (row_shl / row_shr / quad_perm / row_half_mirror) instead of LDS permutes; tree order instead of torch's left-to-right order,
-      // a difference of fp32 round-off under a bf16-grade network output
-      const float znext = dpp_mov<0x101>(zc);                                       // row_shl:1
-      float dist = (s < 7) ? ieee_sub(znext, zc) : 1e10f;                          // trt.py:579-581
-      dist = ieee_mul(dist, dn);                                                   // :583
-      const float cr = sigmoid_fast(r0), cg = sigmoid_fast(r1), cbv = sigmoid_fast(r2);   // :585
-      const float sg = fmaxf(ieee_add(a.noise ? ieee_add(r3, e_noise[cb]) : r3, ad), 0.f);     // refine2.py:508
-      float alpha = ieee_sub(1.f, __expf(ieee_mul(-sg, dist)));                   // :577,587
-      if (a.mul) alpha = ieee_mul(alpha, fmaxf(mu, 0.f));                          // :588
-      const float xk = ieee_add(ieee_sub(1.f, alpha), 1e-10f);                    // :590
-      // exclusive cumprod: shift by one (row_shr:1), then scan.  Every lane move is executed by all lanes and selected afterwards: under
-      // a branch the lanes switched off would read as zero in their neighbours' moves
-      const float xprev = dpp_mov<0x111>(xk);
-      float T = s >= 1 ? xprev : 1.f;
-      { const float t = dpp_mov<0x111>(T); T = ieee_mul(T, s >= 1 ? t : 1.f); }
-      { const float t = dpp_mov<0x112>(T); T = ieee_mul(T, s >= 2 ? t : 1.f); }
-      { const float t = dpp_mov<0x114>(T); T = ieee_mul(T, s >= 4 ? t : 1.f); }
-      const float wgt = ieee_mul(alpha, T);
-      float s0 = sum8_dpp(ieee_mul(wgt, cr)), s1 = sum8_dpp(ieee_mul(wgt, cg)), s2 = sum8_dpp(ieee_mul(wgt, cbv));    // :591 sum over samples
-      const float s3 = sum8_dpp(ieee_mul(wgt, zc));                                // :593 depth_map
-      const float sa = a.white_bkgd ? sum8_dpp(wgt) : 0.f;                          // acc_map
-      if (a.white_bkgd) {                                                           // refine2.py:519-520
-        const float bg = ieee_sub(1.f, sa);
-        s0 = ieee_add(s0, bg); s1 = ieee_add(s1, bg); s2 = ieee_add(s2, bg);
-      }
+      const float4 px = composite8_dpp(a, r0, r1, r2, r3, e_dn[cb], e_z[cb], e_add[cb], e_mul[cb], e_noise[cb], s);
+      const float s0 = px.x, s1 = px.y, s2 = px.z, s3 = px.w;
       if (valid[cb] && g == 0 && s == 0) *(float4*)(a.rgbd + ray * 4) = make_float4(s0, s1, s2, s3);
     });
     if (a.queue) {
@@ -1979,6 +2010,96 @@ __global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfA
   if (a.queue && threadIdx.x == 0) {
     if (atomicAdd(a.queue + 1, 1) == (int)gridDim.x - 1) { a.queue[0] = 0; a.queue[1] = 0; }
   }
+}
+
+template <bool CLS, int NCB = 2, class P = PrecBf16, int NW = 16 / NCB>
+__global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_kernel(NerfArgs a) {
+  nerf16_body<CLS, NCB, P, NW, false>(a);
+}
+template <bool CLS, int NCB = 2, class P = PrecBf16, int NW = 16 / NCB>
+__global__ __launch_bounds__(64 * NW, NCB == 2 ? 2 : 1) void nerf16_list_kernel(NerfArgs a) {
+  nerf16_body<CLS, NCB, P, NW, true>(a);
+}
+
+// ---- compacted-column path: live list and compositing ------------------------------------------------------------------------------------------------------
+// nerf_live_list_kernel: the columns (ray * 8 + s) whose sampler gate is open, mul > 0 — a NaN is closed, as fmaxf(mul, 0) makes it in the compositing —, appended
+// to list[] in any order (a column's result does not depend on where it sits).  A thread takes four consecutive columns of each of LIVE_TILES tiles of 1024, all
+// loads in flight at once: one ballot per component gives a lane its place in the wave, four wave totals in LDS its place in the workgroup, and ONE atomic per
+// workgroup both reserves the range and counts the workgroup: a 64-bit add on the word pair (RUN, DONE), live count in the low word, 1 in the high.  Atomics
+// with a result on one address go through L2 one after the other, some 20 ns each: with a workgroup per 1024 columns and two of them (5 954 workgroups on the
+// 762 048-ray frame) the kernel took 0.245 ms, which was those atomics and nothing else.  The workgroup whose add finds DONE = grid - 1 is the last to
+// reserve: it publishes the live count and the mode word — LIST if force, or if dead * 100 >= dead_percent * total — and puts the pair back to zero for the
+// next launch on this context (no memset on the stream, as the sampler passes and the NeRF queue do it).  It need not wait for the others' list writes: the
+// kernels that read the list come behind this one on the stream.
+constexpr int LIVE_TILES = 8;
+__global__ __launch_bounds__(256) void nerf_live_list_kernel(const float* __restrict__ mul, int64_t ncols, int* __restrict__ list, int* skip, int force, int dead_percent) {
+  __shared__ int s_cnt[4], s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t c0[LIVE_TILES];
+  float4 m[LIVE_TILES];
+#pragma unroll
+  for (int t = 0; t < LIVE_TILES; ++t) {                                     // ncols is a multiple of 8: a thread's four columns are all inside or all outside
+    c0[t] = (((int64_t)blockIdx.x * LIVE_TILES + t) * 256 + threadIdx.x) * 4;
+    m[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c0[t] < ncols) m[t] = *(const float4*)(mul + c0[t]);
+  }
+  int place[LIVE_TILES][4], total = 0;
+#pragma unroll
+  for (int t = 0; t < LIVE_TILES; ++t) {
+    const float mv[4] = {m[t].x, m[t].y, m[t].z, m[t].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long b = __ballot(mv[j] > 0.f);
+      place[t][j] = total + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+      total += __popcll(b);
+    }
+  }
+  if (lane == 0) s_cnt[wave] = total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int mine = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];               // (live <= ncols < 2^31: the low word never carries into the high one)
+    const unsigned long long old = atomicAdd((unsigned long long*)(skip + SKIP_RUN), (1ull << 32) | (unsigned long long)(unsigned)mine);
+    s_base = (int)(unsigned)old;
+    if ((int)(old >> 32) == (int)gridDim.x - 1) {
+      const int64_t live = (int64_t)(unsigned)old + mine;
+      skip[SKIP_LIVE] = (int)live;
+      skip[SKIP_MODE] = (force || (ncols - live) * 100 >= (int64_t)dead_percent * ncols) ? SKIP_MODE_LIST : SKIP_MODE_DENSE;
+      skip[SKIP_RUN] = 0; skip[SKIP_DONE] = 0;
+    }
+  }
+  __syncthreads();
+  int base = s_base;
+  for (int w = 0; w < wave; ++w) base += s_cnt[w];
+#pragma unroll
+  for (int t = 0; t < LIVE_TILES; ++t) {
+    const float mv[4] = {m[t].x, m[t].y, m[t].z, m[t].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (mv[j] > 0.f) list[base + place[t][j]] = (int)(c0[t] + j);
+  }
+}
+
+// nerf_composite_kernel: the compositing behind nerf16_list_kernel, a lane per sample, 8 adjacent lanes a ray — the lane layout and the arithmetic of the fused
+// epilogue (composite8_dpp).  A dead sample (mul <= 0 or NaN) has no entry in raw[]: it takes raw = 0 instead of a load — its alpha is (1 - exp(.)) * 0 = +0 whatever
+// a finite raw is, and so are its four products.
+__global__ __launch_bounds__(256) void nerf_composite_kernel(NerfArgs a) {
+  if (a.skip[SKIP_MODE] != SKIP_MODE_LIST) return;
+  const int64_t ncols = a.n * 8;
+  const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = col < ncols;                                                   // (ncols is a multiple of 8: a ray's 8 lanes are valid together)
+  const int64_t rr = valid ? col : ncols - 1;
+  const float* ry = a.rays + (rr >> 3) * 11;
+  const float dn = ray_dir_norm(ry);
+  const float zc = a.z[rr], ad = a.add[rr], mu = a.mul[rr];
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+  // raw = 0 stands in for the skipped evaluation.  The same bits as with the real raw need (1 - exp(-relu(sigma + add) * dist)) finite, since it is then
+  // multiplied by relu(mul) = 0: dist >= 0 and finite (the refine stage keeps each depth inside its own interval between the midpoints, so z is monotone; equal
+  // z give dist = 0, alpha = +0) and a finite raw — with dist < 0 and a large sigma the dense path's exp overflows and its 0 * inf is a NaN, here it is 0, and a
+  // NaN / inf raw of a diverged net likewise reaches rgbd on the dense path only (include/pronerf_hip.h says so).  Nothing here enforces either: they are properties of the refine stage and of the net.
+  if (mu > 0.f) r = *(const float4*)(a.raw + rr * 4);
+  const int s = (int)(rr & 7);
+  const float4 px = composite8_dpp(a, r.x, r.y, r.z, r.w, dn, zc, ad, mu, 0.f, s);
+  if (valid && s == 0) *(float4*)(a.rgbd + (rr >> 3) * 4) = px;
 }
 
 // ------------------------------------------------------------------------------------------ launch helpers
@@ -2296,18 +2417,33 @@ extern "C" int pnrf_nerf_train_fwd(const pnrf_mlp_t* h, const float* pts, const 
 int pnrf_nerf_fwd_queue_impl(const pnrf_mlp_t* h, const float* pts, const float* rays, const float* z,
                              const float* add_sorted, const float* mul_sorted, const float* noise, float clampv, int white_bkgd,
                              int S, float* rgbd, float* raw, int64_t n, int* queue, void* stream) {
+  return pnrf_nerf_fwd_skip_impl(h, pts, rays, z, add_sorted, mul_sorted, noise, clampv, white_bkgd, S, rgbd, raw, n, queue, nullptr, nullptr, 0, stream);
+}
+
+bool pnrf_nerf_skip_supported(const pnrf_mlp_t* h) { return h && (h->variant == PNRF_VARIANT_DEFAULT || h->variant == PNRF_VARIANT_F16); }
+
+// skip != NULL (a context's large calls, S == 8, rgbd, add / mul; pnrf_nerf_skip_supported): the compacted-column path.  Four launches — the live-list
+// builder, the dense kernel (leaves at once if the builder chose LIST), the list kernel and the compositing pass (leave at once if it chose DENSE); the host
+// reads nothing back.  skip: four ints of the context (SKIP_*), list: [n * 8] ints, raw: [n * 8, 4] floats of the context's workspace (not an output here).
+int pnrf_nerf_fwd_skip_impl(const pnrf_mlp_t* h, const float* pts, const float* rays, const float* z,
+                            const float* add_sorted, const float* mul_sorted, const float* noise, float clampv, int white_bkgd,
+                            int S, float* rgbd, float* raw, int64_t n, int* queue, int* skip, int* list, int force_list, void* stream) {
   PNRF_REQUIRE(h && (h->net == PNRF_NET_NERF || h->net == PNRF_NET_NERFCLS), PNRF_E_ARG, "pnrf_nerf_fwd: handle is not a nerf net");
   PNRF_REQUIRE(n >= 0 && S >= 1 && (n == 0 || (pts && rays)), PNRF_E_ARG, "pnrf_nerf_fwd: null pointer / negative n / bad S");
   PNRF_REQUIRE(n == 0 || (S == 8 ? ((rgbd && z) || raw) : (raw && !rgbd)), PNRF_E_ARG,
                "pnrf_nerf_train_fwd: S == 8 needs rgbd (+z) or raw; S != 8 writes raw only (composite with pnrf_composite_fwd)");
   PNRF_REQUIRE((add_sorted == nullptr) == (mul_sorted == nullptr), PNRF_E_ARG, "pnrf_nerf_train_fwd: add and mul go together");
+  PNRF_REQUIRE(!skip || (pnrf_nerf_skip_supported(h) && S == 8 && rgbd && z && mul_sorted && raw && list && queue && !noise && clampv == 0.f && !white_bkgd &&
+                         n * 8 < ((int64_t)1 << 31)),
+               PNRF_E_ARG, "pnrf_nerf_fwd: the compacted-column path needs the default engine, S == 8, rgbd, z, add / mul, a queue and its workspace");
   if (n == 0) return 0;
   NerfArgs a = {};
   a.blob = h->d_blob; a.bias = h->d_bias; a.nslots = h->nslots; a.nbias = h->nbias;
   a.n = n;
-  a.pts = pts; a.rays = rays; a.z = z; a.add = add_sorted; a.mul = mul_sorted; a.rgbd = rgbd; a.raw = raw;
+  a.pts = pts; a.rays = rays; a.z = z; a.add = add_sorted; a.mul = mul_sorted; a.rgbd = rgbd; a.raw = skip ? nullptr : raw;
   a.noise = noise; a.white_bkgd = white_bkgd; a.clampv = clampv; a.S = S; a.nhid = h->nhid;
   a.queue = h->variant == PNRF_VARIANT_BF16_32X32 ? nullptr : queue;          // (nerf_kernel, the 32x32x16 variant, keeps the static stride)
+  a.skip = skip;
   const size_t lds = RING_BYTES + (size_t)h->nbias * 4;
   const int rows = 256;
   a.nbatch = (int)((n * S + rows - 1) / rows);
@@ -2322,21 +2458,41 @@ int pnrf_nerf_fwd_queue_impl(const pnrf_mlp_t* h, const float* pts, const float*
   // the 16x16x32 engine (two 16-column blocks per wave) in its two workgroup shapes: 256 rows (8 waves) or 128 rows (4 waves) per batch
   const bool narrow = b16 && h->variant != PNRF_VARIANT_NERF_4X64 && stage_shape(h, n * S, 32) == SHAPE_NARROW;
   if (narrow) a.nbatch = (int)((n * S + 127) / 128);
-  if (h->net == PNRF_NET_NERFCLS) {
-    if (narrow) return f16 ? launch_mlp(nerf16_kernel<true, 2, PrecF16, 4>, a, 256, narrow_lds(lds16), a.nbatch, st)
-                           : launch_mlp(nerf16_kernel<true, 2, PrecBf16, 4>, a, 256, narrow_lds(lds16), a.nbatch, st);
-    if (f16) return launch_mlp(nerf16_kernel<true, 2, PrecF16>, a, 512, lds16, a.nbatch, st);
-    if (h->variant == PNRF_VARIANT_NERF_4X64) return launch_mlp(nerf16_kernel<true, 4>, a, 256, lds16, a.nbatch, st);
-    if (b16) return launch_mlp(nerf16_kernel<true, 2>, a, 512, lds16, a.nbatch, st);
-    return launch_mlp(nerf_kernel<1, 8, true, true>, a, 512, lds, a.nbatch, st);
+  if (skip) {
+    const int64_t ncols = n * 8;
+    hipLaunchKernelGGL(nerf_live_list_kernel, dim3((unsigned)((ncols + 1024 * LIVE_TILES - 1) / (1024 * LIVE_TILES))), dim3(256), 0, st, mul_sorted, ncols, list, skip, force_list,
+                       PNRF_NERF_SKIP_DEAD_PERCENT);
+    PNRF_LAUNCH_CHECK();
   }
-  if (narrow) return f16 ? launch_mlp(nerf16_kernel<false, 2, PrecF16, 4>, a, 256, narrow_lds(lds16), a.nbatch, st)
-                         : launch_mlp(nerf16_kernel<false, 2, PrecBf16, 4>, a, 256, narrow_lds(lds16), a.nbatch, st);
-  if (f16) return launch_mlp(nerf16_kernel<false, 2, PrecF16>, a, 512, lds16, a.nbatch, st);
-  if (h->variant == PNRF_VARIANT_NERF_4X64) return launch_mlp(nerf16_kernel<false, 4>, a, 256, lds16, a.nbatch, st);
-  if (b16) return launch_mlp(nerf16_kernel<false, 2>, a, 512, lds16, a.nbatch, st);
-  PNRF_REQUIRE(h->nhid == N_NHID, PNRF_E_SHAPE, "PNRF_VARIANT_BF16_32X32 is built for netdepth %d; this net has netdepth %d — the default engine takes any", N_NHID + 2, h->nhid + 2);
-  return launch_mlp(nerf_kernel<1, 8, true, false>, a, 512, lds, a.nbatch, st);
+  const bool cls = h->net == PNRF_NET_NERFCLS;
+  auto fused = [&](bool list_mode) -> int {
+    NerfArgs b = a;
+    if (list_mode) { b.list = list; b.raw = raw; b.rgbd = nullptr; }
+#define PNRF_NERF16(CLS_, P_, NW_, TPB_, LDS_)                                                                                \
+    (list_mode ? launch_mlp(nerf16_list_kernel<CLS_, 2, P_, NW_>, b, TPB_, LDS_, b.nbatch, st) : launch_mlp(nerf16_kernel<CLS_, 2, P_, NW_>, b, TPB_, LDS_, b.nbatch, st))
+    if (cls) {
+      if (narrow) return f16 ? PNRF_NERF16(true, PrecF16, 4, 256, narrow_lds(lds16)) : PNRF_NERF16(true, PrecBf16, 4, 256, narrow_lds(lds16));
+      if (f16) return PNRF_NERF16(true, PrecF16, 8, 512, lds16);
+      if (h->variant == PNRF_VARIANT_NERF_4X64) return launch_mlp(nerf16_kernel<true, 4>, b, 256, lds16, b.nbatch, st);
+      if (b16) return PNRF_NERF16(true, PrecBf16, 8, 512, lds16);
+      return launch_mlp(nerf_kernel<1, 8, true, true>, b, 512, lds, b.nbatch, st);
+    }
+    if (narrow) return f16 ? PNRF_NERF16(false, PrecF16, 4, 256, narrow_lds(lds16)) : PNRF_NERF16(false, PrecBf16, 4, 256, narrow_lds(lds16));
+    if (f16) return PNRF_NERF16(false, PrecF16, 8, 512, lds16);
+    if (h->variant == PNRF_VARIANT_NERF_4X64) return launch_mlp(nerf16_kernel<false, 4>, b, 256, lds16, b.nbatch, st);
+    if (b16) return PNRF_NERF16(false, PrecBf16, 8, 512, lds16);
+#undef PNRF_NERF16
+    PNRF_REQUIRE(h->nhid == N_NHID, PNRF_E_SHAPE, "PNRF_VARIANT_BF16_32X32 is built for netdepth %d; this net has netdepth %d — the default engine takes any", N_NHID + 2, h->nhid + 2);
+    return launch_mlp(nerf_kernel<1, 8, true, false>, b, 512, lds, b.nbatch, st);
+  };
+  if (int rc = fused(false)) return rc;
+  if (!skip) return 0;
+  if (int rc = fused(true)) return rc;
+  NerfArgs c = a;
+  c.raw = raw;
+  hipLaunchKernelGGL(nerf_composite_kernel, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, st, c);
+  PNRF_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int pnrf_mlp_fwd(const pnrf_mlp_t* h, const float* x, const float* x_views, float* y, int64_t m, int head_act, void* stream) {

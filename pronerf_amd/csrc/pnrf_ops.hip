@@ -721,6 +721,9 @@ struct pnrf_ctx {
   int prof_cap, prof_n;
   bool prof_on;
   float kappa;           // two-pass sampler threshold (pnrf_ctx_set_sampler_kappa); < 0 = PNRF_SAMPLER_KAPPA
+  int nerf_skip;         // PNRF_NERF_SKIP_* (pnrf_ctx_set_nerf_skip)
+  bool skip_last;        // the most recent call took that path (its live count and mode word are in the header)
+  void* skip_ws;         // compacted-column path of the NeRF stage: live list [max_rays * 8] ints, then raw [max_rays * 8, 4] floats; allocated by the first call that takes it
 };
 static constexpr int PROF_EVENTS = 4;
 static constexpr int PROF_MAX_FRAMES = 4096;
@@ -742,6 +745,7 @@ extern "C" int pnrf_ctx_create(const pnrf_mlp_t* sampler, const pnrf_mlp_t* refi
   c->sampler = sampler; c->refine = refine; c->nerf = nerf; c->max_rays = max_rays; c->ws = nullptr;
   c->ev = nullptr; c->prof_cap = 0; c->prof_n = 0; c->prof_on = false;
   c->kappa = -1.f; c->sampler_ws_clean = false;
+  c->nerf_skip = PNRF_NERF_SKIP_AUTO; c->skip_ws = nullptr; c->skip_last = false;
   hipError_t e = hipGetDevice(&c->device);
   PNRF_REQUIRE(max_rays < ((int64_t)1 << 31), PNRF_E_ARG, "pnrf_ctx_create: at most 2^31 - 1 rays per context");
   const size_t ws_rays = (((size_t)max_rays * WS_FLOATS_PER_RAY * sizeof(float)) + 255) & ~(size_t)255;
@@ -763,8 +767,22 @@ extern "C" int pnrf_ctx_create(const pnrf_mlp_t* sampler, const pnrf_mlp_t* refi
 extern "C" int pnrf_ctx_free(pnrf_ctx_t* c) {
   if (!c) return 0;
   if (c->ws) (void)hipFree(c->ws);
+  if (c->skip_ws) (void)hipFree(c->skip_ws);
   profile_release(c);
   delete c;
+  return 0;
+}
+
+// Workspace of the NeRF stage's compacted-column path: live list [cap * 8] ints, then raw [cap * 8, 4] floats (160 bytes per ray)
+static constexpr int64_t SKIP_MAX_RAYS = ((int64_t)1 << 28) - 1;          // ray * 8 + s fits an int32
+static int skip_ws_alloc(pnrf_ctx_t* c, int64_t cap) {
+  if (c->skip_ws) return 0;
+  hipError_t e = hipMalloc(&c->skip_ws, (size_t)cap * 8 * (sizeof(int) + 4 * sizeof(float)));
+  if (e != hipSuccess) {
+    c->skip_ws = nullptr;
+    set_error("allocating the NeRF stage's live-column workspace (%lld rays) failed: %s", (long long)cap, hipGetErrorString(e));
+    return (int)e;
+  }
   return 0;
 }
 
@@ -800,7 +818,32 @@ extern "C" int pnrf_render_rays_fwd(pnrf_ctx_t* c, const float* rays, const floa
   if (ev) PNRF_HIP(hipEventRecord(ev[2], st));
   // NeRF stage with its batches handed out dynamically (words 8, 9 of the sampler workspace's 16-word header: zero since creation, left at zero
   // by every launch): a workgroup that another stream's kernel keeps off its CU for a while does not hold the frame up with its whole share
-  if ((rc = pnrf_nerf_fwd_queue_impl(c->nerf, pts, rays, z, add, mul, nullptr, 0.f, 0, 8, rgbd, nullptr, n, (int*)c->sampler_ws + 8, stream))) return rc;   // :691-694
+  // Large calls (more than one wide batch per CU: throughput, not latency, sets their time) evaluate only the columns whose sampler gate is open (mul > 0: the
+  // others' alpha is exactly 0) when enough are closed to pay for the extra passes: words 10 .. 13 of the header, pnrf_nerf_fwd_skip_impl.  Same rgbd bit for bit.
+  // The list holds int32 column ids: a call of 2^28 rays or more stays on the fused kernel, which indexes in 64 bits.
+  const int64_t skip_cap = c->max_rays < SKIP_MAX_RAYS ? c->max_rays : SKIP_MAX_RAYS;
+  bool skip = pnrf_nerf_skip_supported(c->nerf) && n <= SKIP_MAX_RAYS &&
+              (c->nerf_skip == PNRF_NERF_SKIP_ALWAYS || (c->nerf_skip == PNRF_NERF_SKIP_AUTO && n > PNRF_NERF_SKIP_MIN_RAYS));
+  if (skip && !c->skip_ws) {                               // the first such call of a context allocates its workspace ...
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PNRF_HIP(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) {               // ... but never inside a stream capture, which an allocation would invalidate: such a call runs the
+      skip = false;                                        // fused kernel alone, as before (any call outside a capture, or pnrf_ctx_set_nerf_skip, allocates)
+    } else if ((rc = skip_ws_alloc(c, skip_cap))) {
+      return rc;
+    }
+  }
+  int* hdr = (int*)c->sampler_ws;
+  if (skip) {
+    int* list = (int*)c->skip_ws;
+    float* raw_ws = (float*)(list + skip_cap * 8);
+    rc = pnrf_nerf_fwd_skip_impl(c->nerf, pts, rays, z, add, mul, nullptr, 0.f, 0, 8, rgbd, raw_ws, n, hdr + 8, hdr + 10, list,
+                                 c->nerf_skip == PNRF_NERF_SKIP_ALWAYS, stream);
+  } else {
+    rc = pnrf_nerf_fwd_queue_impl(c->nerf, pts, rays, z, add, mul, nullptr, 0.f, 0, 8, rgbd, nullptr, n, hdr + 8, stream);   // :691-694
+  }
+  if (rc) return rc;
+  c->skip_last = skip;
   if (ev) {
     PNRF_HIP(hipEventRecord(ev[3], st));
     c->prof_n += 1;
@@ -826,6 +869,29 @@ extern "C" int pnrf_ctx_sampler_stats(pnrf_ctx_t* c, int64_t* rays_second_pass) 
   int v[2] = {0, 0};
   PNRF_HIP(hipMemcpy(v, c->sampler_ws, sizeof(v), hipMemcpyDeviceToHost));       // synchronises with the device: diagnostics only
   *rays_second_pass = v[1];
+  return 0;
+}
+
+extern "C" int pnrf_ctx_set_nerf_skip(pnrf_ctx_t* c, int mode) {
+  PNRF_REQUIRE(c, PNRF_E_ARG, "pnrf_ctx_set_nerf_skip: null context");
+  PNRF_REQUIRE(mode == PNRF_NERF_SKIP_NEVER || mode == PNRF_NERF_SKIP_AUTO || mode == PNRF_NERF_SKIP_ALWAYS, PNRF_E_ARG,
+               "pnrf_ctx_set_nerf_skip: mode must be 0 (never), 1 (auto) or 2 (always), got %d", mode);
+  c->nerf_skip = mode;
+  // the workspace now, if this context's calls can take the path at all, so that a first large call inside a stream capture finds it
+  int cur = -1;
+  PNRF_HIP(hipGetDevice(&cur));
+  if (cur == c->device && pnrf_nerf_skip_supported(c->nerf) &&
+      (mode == PNRF_NERF_SKIP_ALWAYS || (mode == PNRF_NERF_SKIP_AUTO && c->max_rays > PNRF_NERF_SKIP_MIN_RAYS)))
+    return skip_ws_alloc(c, c->max_rays < SKIP_MAX_RAYS ? c->max_rays : SKIP_MAX_RAYS);
+  return 0;
+}
+
+extern "C" int pnrf_ctx_nerf_live(pnrf_ctx_t* c, int64_t* live_columns, int* list_mode) {
+  PNRF_REQUIRE(c && live_columns && list_mode, PNRF_E_ARG, "pnrf_ctx_nerf_live: null argument");
+  int v[16] = {0};
+  PNRF_HIP(hipMemcpy(v, c->sampler_ws, sizeof(v), hipMemcpyDeviceToHost));       // synchronises with the device: diagnostics only
+  *live_columns = c->skip_last ? v[12] : -1;
+  *list_mode = c->skip_last ? v[13] : 0;
   return 0;
 }
 

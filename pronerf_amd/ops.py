@@ -431,6 +431,20 @@ class RenderContext:
         check(_lib.load().pnrf_ctx_get_sampler_kappa(self.handle, C.byref(v)), 'pnrf_ctx_get_sampler_kappa')
         return float(v.value)
 
+    NERF_SKIP = {'never': 0, 'auto': 1, 'always': 2}
+
+    def set_nerf_skip(self, mode):
+        """NeRF stage of render_rays (pnrf_ctx_set_nerf_skip): 'never' = the fused kernel alone, 'auto' (a new context) = large calls evaluate only the samples
+        whose sampler gate is open (mul > 0) when enough are closed, 'always' = that path whatever the call size or share.  Same rgbd bit for bit."""
+        check(_lib.load().pnrf_ctx_set_nerf_skip(self.handle, int(self.NERF_SKIP.get(mode, mode))), 'pnrf_ctx_set_nerf_skip')
+
+    def nerf_live(self):
+        """-> (live columns, list mode) of the most recent render_rays call (pnrf_ctx_nerf_live): samples with mul > 0 the builder counted (-1 if the call
+        did not take the compacted-column path) and whether the MLP ran over the list; waits for the device."""
+        v, m = C.c_int64(), C.c_int()
+        check(_lib.load().pnrf_ctx_nerf_live(self.handle, C.byref(v), C.byref(m)), 'pnrf_ctx_nerf_live')
+        return int(v.value), bool(m.value)
+
     def profile_begin(self, max_frames=64):
         """Record per-stage events on the next ``max_frames`` render_rays calls (pnrf_ctx_profile_begin)."""
         check(_lib.load().pnrf_ctx_profile_begin(self.handle, int(max_frames)), 'pnrf_ctx_profile_begin')

@@ -6,7 +6,9 @@
 A config selects a library build (lib=<name> -> pronerf_amd/lib/libpronerf_hip_<name>.so, empty = the default build; see
 `python -m pronerf_amd.build --variant <name> [flags]`) and the kernel variants of its handles (pnrf_mlp_set_variant: sampler=
 default (two passes) | sampler_split | sampler_f32 | sampler_f32_full, refine= default (fp16) | bf16 | refine_16x16, nerf= default (fp16) | bf16 | bf16_32x32 | nerf_4x64) — explicit configuration, the library reads no environment.  shape=wide|narrow|single forces the workgroup shape of all three
-stages (pnrf_mlp_set_shape).
+stages (pnrf_mlp_set_shape).  skip=never|auto|always sets the NeRF stage's compacted-column path (pnrf_ctx_set_nerf_skip; a library without the entry point
+takes no skip=).  --weights picks the nets: a kind of synthetic.make_weights or a trained fixture ('pictures' | 'scene3d'), on the same frame.  Naming one
+config twice (lib=parent;lib=parent;lib=) gives the A/B's own spread: the difference between two identical configs, printed as 'pair spread'.
 Every round renders `--frames` frames per config through pnrf_render_rays_fwd with the context's per-kernel events
 (pnrf_ctx_profile_begin / _end); reports median / min over the rounds per stage kernel on the bench workload (one 1008x756 frame).
 path=ops times the operator-level sequence instead (sampler, refine_input, refine on refine_in, NeRF: four kernels with the [n,144]
@@ -41,10 +43,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--frames', type=int, default=10)
+    ap.add_argument('--weights', default='trained')
     ap.add_argument('--configs', default='lib=;lib=,sampler=sampler_split;lib=,nerf=bf16_32x32')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
-    weights = synthetic.make_weights(0, 'trained')
+    weights = synthetic.load_trained_fixture(a.weights) if a.weights in synthetic.FIXTURES else synthetic.make_weights(0, a.weights)
     scene = synthetic.make_scene(0, H=H, W=W, focal=815.13, rotate=True)
     cfgs = [dict(kv.split('=') for kv in c.split(',') if kv) for c in a.configs.split(';')]
     libs, rends = {}, []
@@ -56,6 +59,8 @@ def main():
         var = {k: v for k, v in (('sampler', c.get('sampler', 'default')), ('refine', c.get('refine', 'default')), ('nerf', c.get('nerf', 'default'))) if v != 'default'}
         r = Renderer(weights, max_rays=H * W, device=dev, variants=var, shape=(c.get('shape') or None))
         r.set_views(scene['c2w'], scene['poses'], scene['images'], scene['K'])
+        if c.get('skip'):
+            r.ctx.set_nerf_skip(c['skip'])
         rends.append(r)
     _lib._lib = libs[cfgs[0].get('lib', '')]
     rays, or_rays = rends[0].frame_rays(scene['K'], scene['c2w'], H, W)
@@ -92,7 +97,20 @@ def main():
             res[i].setdefault('frame', []).append(sum(ms.values()))
     for i, c in enumerate(cfgs):
         line = ' '.join(f'{k}={statistics.median(v):.3f}/{min(v):.3f}' for k, v in res[i].items())
-        print(f'{c}: median/min ms  {line}')
+        live = ''
+        if hasattr(libs[c.get('lib', '')], 'pnrf_ctx_nerf_live'):
+            _lib._lib = libs[c.get('lib', '')]
+            n_live, list_mode = rends[i].ctx.nerf_live()
+            live = f'  live columns {n_live} of {H * W * 8}, list mode {list_mode}'
+        print(f'{a.weights} {c}: median/min ms  {line}{live}')
+    # identical configs: the spread of the comparison itself (largest difference of their medians and of their per-round values)
+    for i, c in enumerate(cfgs):
+        for j in range(i + 1, len(cfgs)):
+            if cfgs[j] == c:
+                for k in ('nerf_kernel', 'frame'):
+                    d = [x - y for x, y in zip(res[i][k], res[j][k])]
+                    print(f'{a.weights} pair spread {k}: medians differ by {abs(statistics.median(res[i][k]) - statistics.median(res[j][k])):.4f} ms, '
+                          f'rounds by {min(d):+.4f} .. {max(d):+.4f} ms')
 
 
 if __name__ == '__main__':
