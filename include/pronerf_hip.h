@@ -565,6 +565,43 @@ int pnrf_render_pose_fwd(pnrf_ctx_t* ctx, const pnrf_scene_t* s, const float* c2
                          float or_far, int64_t first, int64_t block, int64_t stride, int64_t count, float eps, void* ws, int64_t ws_bytes,
                          float* rgbd, int64_t* sort_idx, void* stream);
 
+/* ---- device-resident training set: a batch from ray indices alone ------------------------------------
+ * What the training drivers do per iteration on the host side (run_S_eS_eN_alter_base_refine2.py / ..._base.py: three row gathers out of per-pixel
+ * arrays of every training view, a fancy-index chain for ref_nos, a host-to-device copy of the neighbour draw, the jitter / noise kernels) from a
+ * PNRF_SCENE_F32 scene of the training views.  Ray g of the training set is view g / (Hf Wf), pixel g % (Hf Wf).
+ *
+ * Device addresses of a COMPLETE PNRF_SCENE_F32 scene (any output may be NULL): img4 [nv,Hf,Wf,4] — bit for bit what pnrf_images_pack makes of the
+ * views, so it is pnrf_train_batch_t.img4 as it stands — poses [nv,3,4], K_target [3,3], K_ref [3,3].  Valid until pnrf_scene_free.  PNRF_E_STATE if a
+ * view or the intrinsics are missing; PNRF_E_ARG for a PNRF_SCENE_U8 scene (the trainer reads fp32 texels). */
+int pnrf_scene_arrays(const pnrf_scene_t* s, const float** img4, const float** poses, const float** K_target, const float** K_ref);
+/* rank dev int32 [nv,nv]: row c = the views in stable ascending order of their distance to view c — the ranking of pnrf_scene_select_fwd (one shared
+ * device function: same arithmetic, ties to the lower index, NaN last) with view c's camera centre as the target, one workgroup per row; equal to
+ * neighbor_rank_table of the stage-2 driver index for index (rank[c][0] is c itself unless another view shares its position). */
+int pnrf_scene_rank_table_fwd(const pnrf_scene_t* s, int32_t* rank, void* stream);
+/* The batch of the n rays idx dev int64 [n], at most two launches, nothing allocated, nothing read back; all outputs dev, caller-owned:
+ *   rays, or_rays [n,11]  the rows pnrf_frame_rays_fwd writes for (K_target, pose of the ray's view, Hf, Wf, near, far, or_near, or_far) at the ray's
+ *                         pixel, bit for bit (the shared per-pixel body, csrc/pnrf_frame_rays.h, with a per-row camera)
+ *   target [n,3]          the texel's r, g, b, copied
+ *   ref_nos int64 [n,4]   rank[view][1 + order[k]]; order: HOST int[4], 0 <= order[k] < nv - 1 (the driver's sorted random.sample; it travels in the
+ *                         kernel arguments); rank: the table above (entries are clamped into 0 .. nv - 1 when read)
+ *   jitter [n,jitter_cols] = fminf(|z| / 5, jitter_cap), noise [n,noise_cols] = z noise_std, z ~ N(0,1); NULL skips the draw; columns: multiples of
+ *                         4 up to 256; 16-byte aligned.
+ * An idx outside [0, nv Hf Wf) reads nothing out of range: its row gets NaN rays and target, ref_nos 0, and bad_rows (dev int64, optional) is
+ * incremented once per such row (atomicAdd; the caller zeroes it).
+ * Draws: Philox4x32-10 (pnrf_philox4x32_10 below), key = (seed low word, seed high word); the quad q = (row0 + row) (C / 4) + k of an array with C
+ * columns takes counter (q low, q high, step, stream), stream 0 = jitter, 1 = noise, and fills columns 4k .. 4k + 3 of its row: word x -> u =
+ * (2 (x >> 9) + 1) 2^-24 (exact, inside (0, 1)); words (0, 1) and (2, 3) each give r = sqrt(-2 logf(u0)), (r cospi(2 u1), r sinpi(2 u1)), accurate
+ * library functions.  row0: the batch row of the caller's first row (a data-parallel replica passes replica n_local: the union of the replicas'
+ * draws does not depend on the world size).  Deterministic in (seed, step, row); not torch's stream.
+ * Checked before any device work (PNRF_E_ARG): nv < 5, order out of range, n < 0, a null required pointer, bad column counts. */
+int pnrf_train_batch_fwd(const pnrf_scene_t* s, const int32_t* rank, const int64_t* idx, int64_t n, const int* order, float near, float far,
+                         float or_near, float or_far, float* rays, float* or_rays, float* target, int64_t* ref_nos, int64_t* bad_rows,
+                         uint64_t seed, uint32_t step, int64_t row0, float* jitter, int jitter_cols, float jitter_cap, float* noise,
+                         int noise_cols, float noise_std, void* stream);
+/* Host helper: one Philox4x32-10 block (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), the code the draws above run.
+ * counter HOST [4], key HOST [2], out HOST [4].  counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8. */
+int pnrf_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+
 /* Host helper: torch.linspace(start,end,n) in fp32, as used for the 48 ray points
  * (run_S_eS_eN_alter_trt.py:556-557).  out: HOST [n]. */
 int pnrf_linspace(float start, float end, int n, float* out);

@@ -84,6 +84,11 @@ SIGNATURES = {
     'pnrf_frame_rays_dev_fwd': (_i, [_p, _p, _i, _i, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _p, _p, _p]),
     'pnrf_render_pose_workspace_bytes': (_i, [_p, _i, _i64, C.POINTER(_i64)]),
     'pnrf_render_pose_fwd': (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _f, _p, _i64, _p, _p, _p]),
+    # device-resident training set: ray indices -> batch
+    'pnrf_scene_arrays': (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
+    'pnrf_scene_rank_table_fwd': (_i, [_p, _p, _p]),
+    'pnrf_train_batch_fwd': (_i, [_p, _p, _p, _i64, C.POINTER(_i), _f, _f, _f, _f, _p, _p, _p, _p, _p, C.c_uint64, C.c_uint32, _i64, _p, _i, _f, _p, _i, _f, _p]),
+    'pnrf_philox4x32_10': (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     # stage-2 training step
     'pnrf_composite_bwd': (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
     'pnrf_posenc_bwd': (_i, [_p, _p, _p, _i64, _i, _p]),

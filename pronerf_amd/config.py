@@ -12,7 +12,7 @@ from __future__ import annotations
 import argparse
 import ast
 
-# name, type ('flag' = store_true, 'ints' = list of int), default — shared by the three scripts
+# name, type ('flag' = store_true, 'ints' = list of int, a tuple of strings = one of these), default — shared by the three scripts
 _COMMON = [
     ('expname', str, None), ('datadir', str, './data/llff/fern'),
     ('netdepth', int, 8), ('netwidth', int, 256), ('netskips', 'ints', [4]),
@@ -31,6 +31,10 @@ _COMMON = [
     ('lindisp', 'flag', False), ('spherify', 'flag', False), ('llffhold', int, 8),
     ('i_print', int, 5000), ('i_img', int, 10000), ('i_weights', int, 10000), ('i_testset', int, 10000), ('i_video', int, 10000),
 ]
+# not in the reference, both training scripts: where a batch is assembled.  'off': per-pixel arrays of every training view, gathered per iteration (the
+# statements of the first release); 'rays': rays, targets and neighbour views from a device-resident scene and the batch's ray indices
+# (ops.TrainSet), jitter and noise from torch as before; 'all': jitter and noise from the device generator too, seeded by batch_seed
+_TRAIN = [('device_batches', ('off', 'rays', 'all'), 'off'), ('batch_seed', int, 0)]
 _VARIANT = {
     # inference (run_S_eS_eN_alter_trt.py): TensorRT / ONNX switches are parsed for config compatibility only
     'trt': [('basedir', str, './logs_trt/'), ('use_trt', 'flag', False), ('export_only', 'flag', False), ('nerf_engine_path', str, None),
@@ -45,9 +49,9 @@ _VARIANT = {
             # pnrf_scene_cache; 'u8': RGBA8 texels, for images that are exact 8-bit values)
             ('scene_cache', str, None)],
     # stage 2 (run_S_eS_eN_alter_base_refine2.py)
-    'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)],
+    'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)] + _TRAIN,
     # stage 1 (run_S_eS_eN_alter_base.py)
-    'base': [('basedir', str, './logs_epi_RR/'), ('epi_nerf', 'flag', False), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)],
+    'base': [('basedir', str, './logs_epi_RR/'), ('epi_nerf', 'flag', False), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)] + _TRAIN,
 }
 
 
@@ -58,6 +62,10 @@ def _convert(kind, text):
     if kind == 'ints':
         v = ast.literal_eval(text) if text.startswith('[') else [int(t) for t in text.replace(',', ' ').split()]
         return [int(x) for x in v]
+    if isinstance(kind, tuple):
+        if text not in kind:
+            raise ValueError(f'expected one of {kind}, got {text!r}')
+        return text
     if text == 'None':
         return None
     return kind(text)
@@ -92,6 +100,8 @@ class ConfigArgumentParser(argparse.ArgumentParser):
                 self.add_argument('--' + name, action='store_true', default=default)
             elif kind == 'ints':
                 self.add_argument('--' + name, type=int, nargs='*', default=default)
+            elif isinstance(kind, tuple):
+                self.add_argument('--' + name, type=str, choices=kind, default=default)
             else:
                 self.add_argument('--' + name, type=kind, default=default)
 

@@ -9,24 +9,14 @@
 
 #include "pnrf_common.h"
 #include "pnrf_frame_rays.h"
+#include "pnrf_scene_impl.h"
 
 using namespace pnrf;
 
-struct pnrf_scene {
-  int nv, Hf, Wf, format;
-  int device;                 // -1 until the first pnrf_scene_set_view / pnrf_scene_set_intrinsics allocates the device arrays
-  void* cache;                // [nv,Hf,Wf] texels: float4 (PNRF_SCENE_F32) or uchar4 (PNRF_SCENE_U8), w = 0
-  float* poses;               // dev [nv,3,4] camera-to-world; a view's row is written by its ingest kernel (the forward calls need every view set)
-  float* K;                   // dev [2,3,3]: K_target, K_ref
-  std::vector<uint8_t> have;  // host: view v has been set
-  int n_have;
-  bool have_K;
-};
-
 namespace {
 
-constexpr int TPB = 256;
-constexpr int MAX_VIEWS = 4096;           // the ranking kernel keeps one distance per view in LDS (16 KiB)
+constexpr int TPB = SCENE_TPB;
+constexpr int MAX_VIEWS = SCENE_MAX_VIEWS;           // the ranking kernel keeps one distance per view in LDS (16 KiB)
 constexpr int SCENE_MAX_NB = 8;
 inline int grid_for(int64_t work) {
   int64_t g = (work + TPB - 1) / TPB;
@@ -65,9 +55,8 @@ __global__ void scene_ingest_kernel(const void* __restrict__ src, int src_u8, in
 }
 
 // Neighbour ranking + projection matrices of one target pose: ONE workgroup.
-//   d[v] = sqrt((dx dx + dy dy) + dz dz) of the camera centres, every operation rounded once (render.select_neighbors: numpy's fp32 element-wise ops and its
-//   three-term sum); rank by counting over the distances in LDS: rank(v) = #{u : d[u] < d[v], or equal and u < v}, a NaN behind every number — the order
-//   of a stable ascending sort (np.argsort(kind='stable')); the views of rank < nb go to ref_nos[rank].
+//   distances and stable ascending ranks as scene_rank_views states them (pnrf_scene_impl.h; shared with the training set's rank table); the views of
+//   rank < nb go to ref_nos[rank].
 //   proj[k] = K_ref . diag(1,-1,-1) . pose[ref_nos[k]]: fp32 x fp32 products are exact in fp64, the left-to-right three-term sum is formed in fp64 and
 //   rounded once to fp32 — the same bits with or without FMA contraction.
 __global__ __launch_bounds__(TPB) void scene_select_kernel(const float* __restrict__ poses, int nv, const float* __restrict__ c2w, const float* __restrict__ Kref,
@@ -75,22 +64,9 @@ __global__ __launch_bounds__(TPB) void scene_select_kernel(const float* __restri
   __shared__ float sd[MAX_VIEWS];
   __shared__ int ssel[SCENE_MAX_NB];
   const int tid = threadIdx.x;
-  const float tx = c2w[3], ty = c2w[7], tz = c2w[11];
-  for (int v = tid; v < nv; v += TPB) {
-    const float* p = poses + (int64_t)v * 12;
-    const float dx = ieee_sub(tx, p[3]), dy = ieee_sub(ty, p[7]), dz = ieee_sub(tz, p[11]);
-    sd[v] = ieee_sqrt(ieee_add(ieee_add(ieee_mul(dx, dx), ieee_mul(dy, dy)), ieee_mul(dz, dz)));
-  }
-  __syncthreads();
-  for (int v = tid; v < nv; v += TPB) {
-    const float d = sd[v];
-    int rank = 0;
-    for (int u = 0; u < nv; ++u) {
-      const float o = sd[u];
-      rank += (o < d || (o == d && u < v) || (d != d && (o == o || u < v))) ? 1 : 0;
-    }
-    if (rank < nb) { ssel[rank] = v; ref_nos[rank] = v; }       // the ranks are a permutation of 0 .. nv - 1 and nb <= nv: every slot is written once
-  }
+  scene_rank_views(poses, nv, c2w[3], c2w[7], c2w[11], sd, [&](int v, int rank) {
+    if (rank < nb) { ssel[rank] = v; ref_nos[rank] = v; }        // the ranks are a permutation of 0 .. nv - 1 and nb <= nv: every slot is written once
+  });
   __syncthreads();
   if (tid < nb * 12) {
     const int k = tid / 12, e = tid - k * 12, r = e >> 2, c = e & 3;

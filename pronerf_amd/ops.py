@@ -582,6 +582,91 @@ class Scene:
         check(_lib.load().pnrf_render_pose_workspace_bytes(self.handle, int(nb), int(max_rays), C.byref(v)), 'pnrf_render_pose_workspace_bytes')
         return int(v.value)
 
+    def arrays(self):
+        """Zero-copy views (img4 [nv,Hf,Wf,4], poses [nv,3,4], K_target [3,3], K_ref [3,3]) of a complete 'f32' scene's device arrays
+        (pnrf_scene_arrays): img4 is bit for bit ``images_pack`` of the views, i.e. what ``Trainer.fwd_bwd`` takes."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        check(_lib.load().pnrf_scene_arrays(self.handle, *[C.byref(p) for p in ptrs]), 'pnrf_scene_arrays')
+        shapes = [(self.nv, self.Hf, self.Wf, 4), (self.nv, 3, 4), (3, 3), (3, 3)]
+        return tuple(_dev_view(int(p.value), sh, '<f4', self.device, self) for p, sh in zip(ptrs, shapes))
+
+    def rank_table(self):
+        """int32 [nv,nv]: row c = the views in stable ascending order of their distance to view c (pnrf_scene_rank_table_fwd) — the stage-2
+        driver's ``neighbor_rank_table`` index for index."""
+        with torch.cuda.device(self.device):
+            rank = torch.empty(self.nv, self.nv, device=self.device, dtype=torch.int32)
+            check(_lib.load().pnrf_scene_rank_table_fwd(self.handle, _ptr(rank), _stream()), 'pnrf_scene_rank_table_fwd')
+        return rank
+
+
+def _dev_view(ptr, shape, typestr, device, owner):
+    """torch tensor over device memory the library owns (``__cuda_array_interface__`` v3: no copy); ``owner`` stays alive as long as the view."""
+    class _Dev:
+        __cuda_array_interface__ = {'shape': tuple(int(x) for x in shape), 'typestr': typestr, 'data': (int(ptr), False), 'version': 3}
+    with torch.cuda.device(device):
+        t = torch.as_tensor(_Dev(), device=device)
+    t._pnrf_owner = owner
+    return t
+
+
+class TrainSet:
+    """The training set of a driver on the device: a complete 'f32' ``Scene`` of the training views, its rank table and persistent output buffers
+    for one batch of at most ``max_rays`` rays (``max_cols`` jitter / noise columns), so that the pointers the trainer sees are the same in every
+    iteration.  ``batch`` turns ray indices (ray g = view g // (Hf Wf), pixel g % (Hf Wf)) into the positional head of ``Trainer.fwd_bwd`` /
+    ``Trainer.explore_fwd_bwd`` with at most two launches (pnrf_train_batch_fwd); nothing per-pixel is ever expanded for the whole set."""
+
+    def __init__(self, scene, max_rays, near, far, or_near=1.0, or_far=10.0, max_cols=8):
+        if not isinstance(scene, Scene):
+            raise PnrfError('TrainSet: expected an ops.Scene')
+        max_rays, max_cols = int(max_rays), int(max_cols)
+        if max_rays < 1 or max_cols < 4 or max_cols % 4 or max_cols > 256:
+            raise PnrfError(f'TrainSet: max_rays >= 1 and max_cols a multiple of 4 in 4 .. 256, got {max_rays}, {max_cols}')
+        self.scene, self.device = scene, scene.device
+        self.max_rays, self.max_cols = max_rays, max_cols
+        self.near, self.far, self.or_near, self.or_far = float(near), float(far), float(or_near), float(or_far)
+        self.img4, self.poses, self.K_target, self.K = scene.arrays()          # K: the source cameras' intrinsics (ref_K), the one the trainer projects with
+        self.device = self.img4.device                                           # with its index, as every tensor's device has it
+        self.rank = scene.rank_table()
+        with torch.cuda.device(self.device):
+            new = lambda *sh, dt=f32: torch.empty(*sh, device=self.device, dtype=dt)
+            self._rays, self._or_rays, self._target = new(max_rays, 11), new(max_rays, 11), new(max_rays, 3)
+            self._ref_nos = new(max_rays, 4, dt=torch.int64)
+            self._jitter, self._noise = new(max_rays * max_cols), new(max_rays * max_cols)
+            self._bad = torch.zeros(1, device=self.device, dtype=torch.int64)
+
+    def batch(self, idx, order, step=None, seed=0, row0=0, jitter_cols=0, jitter_cap=1 - 2e-6, noise_cols=0, noise_std=0.):
+        """idx: int64 GPU tensor [n], n <= max_rays; order: four Python ints in 0 .. nv - 2 (rank positions after dropping the view itself).
+        -> (rays, or_rays, target, img4, poses, K, ref_nos) [+ jitter [n,jitter_cols]] [+ noise [n,noise_cols]]: views of the persistent buffers,
+        valid until the next call.  Draws (jitter_cols / noise_cols > 0) need ``step``; they are a function of (seed, step, row0 + row) alone."""
+        if not isinstance(idx, torch.Tensor) or idx.device != self.device or idx.dtype != torch.int64 or idx.dim() != 1:
+            raise PnrfError(f'TrainSet.batch: idx must be a 1-D int64 tensor on {self.device}')
+        idx = idx.contiguous()
+        n = idx.shape[0]
+        if n > self.max_rays:
+            raise PnrfError(f'TrainSet.batch: {n} rays, the set was sized for {self.max_rays}')
+        cj, cn = int(jitter_cols), int(noise_cols)
+        if max(cj, cn) > self.max_cols or min(cj, cn) < 0:
+            raise PnrfError(f'TrainSet.batch: jitter_cols / noise_cols must be 0 .. max_cols = {self.max_cols}, got {cj}, {cn}')
+        if (cj or cn) and step is None:
+            raise PnrfError('TrainSet.batch: draws need a step')
+        order = [int(o) for o in order]
+        if len(order) != 4:
+            raise PnrfError(f'TrainSet.batch: order must hold 4 rank positions, got {len(order)}')
+        jit = self._jitter[:n * cj].view(n, cj) if cj else None
+        noi = self._noise[:n * cn].view(n, cn) if cn else None
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_train_batch_fwd(self.scene.handle, _ptr(self.rank), _ptr(idx), n, (C.c_int * 4)(*order), self.near, self.far, self.or_near,
+                                                   self.or_far, _ptr(self._rays), _ptr(self._or_rays), _ptr(self._target), _ptr(self._ref_nos),
+                                                   _ptr(self._bad), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step or 0) & 0xFFFFFFFF, int(row0), _ptr(jit), cj,
+                                                   float(jitter_cap), _ptr(noi), cn, float(noise_std), _stream()), 'pnrf_train_batch_fwd')
+            idx.record_stream(torch.cuda.current_stream())
+        out = (self._rays[:n], self._or_rays[:n], self._target[:n], self.img4, self.poses, self.K, self._ref_nos[:n])
+        return out + ((jit,) if cj else ()) + ((noi,) if cn else ())
+
+    def bad_rows(self):
+        """Rows whose index lay outside the set since construction (they got NaN rays and targets).  Synchronises: tests and debugging."""
+        return int(self._bad.item())
+
 
 def linspace(start, end, n):
     out = (C.c_float * n)()

@@ -164,14 +164,20 @@ def train(argv=None, device='cuda'):
     if ck is not None:
         restore_optimizer(tr, ck, 1)
     adam_steps = [start - start // 2, start // 2] if ck is not None and 'pnrf_adam_steps' not in ck else ([0, 0] if ck is None else list(ck['pnrf_adam_steps']))
-    with torch.cuda.device(dev):
-        pr = [ops.frame_rays(K, poses[i], H, W, near=1e-6, far=1., device=dev) for i in i_train]               # near = 1e-6 (:798)
-        rays_all = torch.cat([p[0] for p in pr], 0); or_rays_all = torch.cat([p[1] for p in pr], 0)
-        del pr
-        target_all = torch.as_tensor(images[i_train], dtype=torch.float32).reshape(-1, 3).to(dev)
-        own_all = torch.arange(len(i_train), device=dev).repeat_interleave(H * W)
-        img4, poses_t, K_t, rank = _train_views(images[i_train], poses[i_train], K, dev)
-    n_total = rays_all.shape[0]
+    mode = args.device_batches
+    if mode == 'off':
+        with torch.cuda.device(dev):
+            pr = [ops.frame_rays(K, poses[i], H, W, near=1e-6, far=1., device=dev) for i in i_train]               # near = 1e-6 (:798)
+            rays_all = torch.cat([p[0] for p in pr], 0); or_rays_all = torch.cat([p[1] for p in pr], 0)
+            del pr
+            target_all = torch.as_tensor(images[i_train], dtype=torch.float32).reshape(-1, 3).to(dev)
+            own_all = torch.arange(len(i_train), device=dev).repeat_interleave(H * W)
+            img4, poses_t, K_t, rank = _train_views(images[i_train], poses[i_train], K, dev)
+        n_total = rays_all.shape[0]
+    else:                                                # every batch from its ray indices and the device-resident views (ops.TrainSet)
+        with torch.cuda.device(dev):
+            tset = ops.TrainSet(ops.Scene.from_views(poses[i_train], images[i_train], K, device=dev), n_local, near=1e-6, far=1., max_cols=8 * max_mult)
+        n_total = len(i_train) * H * W
     epoch = 0
     perm = shared_permutation(n_total, epoch, dev) if world > 1 else torch.randperm(n_total, device=dev)
     i_batch, global_step, log = 0, start, []
@@ -187,15 +193,25 @@ def train(argv=None, device='cuda'):
             continue
         idx = idx[replica * n_local:(replica + 1) * n_local]                                                          # this replica's share
         n = idx.shape[0]
-        order = torch.as_tensor(sorted(random.sample(range(nv - 1), 4)), device=dev)                           # :629-634
-        ref_nos = rank[own_all[idx]][:, 1:][:, order].contiguous()
-        batch = (rays_all[idx], or_rays_all[idx], target_all[idx], img4, poses_t, K_t, ref_nos)
+        if mode == 'off':
+            order = torch.as_tensor(sorted(random.sample(range(nv - 1), 4)), device=dev)                       # :629-634
+            ref_nos = rank[own_all[idx]][:, 1:][:, order].contiguous()
+            batch = (rays_all[idx], or_rays_all[idx], target_all[idx], img4, poses_t, K_t, ref_nos)
+        else:
+            order = sorted(random.sample(range(nv - 1), 4))                                                    # four ints: they travel in the kernel arguments
+            batch = tset.batch(idx, order) if mode == 'rays' or i % 2 == 0 else None                           # ('all', odd: one call with the draws below)
         if i % 2 != 0:                                                                                         # :929-940
             n_mult = random.randint(1, max_mult)                                                               # :690-691
             dir1 = (1 if random.random() > 0.5 else -1) if n_mult > 1 else 1
-            jitter = torch.abs(torch.normal(0.0, 1.0, size=(n, 8 * n_mult), device=dev) / 5).clamp(max=0.99)   # :715-719
+            if mode != 'all':
+                jitter = torch.abs(torch.normal(0.0, 1.0, size=(n, 8 * n_mult), device=dev) / 5).clamp(max=0.99)   # :715-719
             dir2 = 1 if random.random() > 0.5 else -1
-            noise = torch.randn(n, 8 * n_mult, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
+            if mode != 'all':
+                noise = torch.randn(n, 8 * n_mult, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
+            else:                                        # jitter and noise from the device generator, a function of (batch_seed, iteration, batch row)
+                out = tset.batch(idx, order, step=i, seed=args.batch_seed, row0=replica * n_local, jitter_cols=8 * n_mult, jitter_cap=0.99,
+                                 noise_cols=8 * n_mult if args.raw_noise_std > 0 else 0, noise_std=args.raw_noise_std)
+                batch, jitter, noise = out[:7], out[7], (out[8] if args.raw_noise_std > 0 else None)
             loss, _ = tr.explore_fwd_bwd(*batch, n_mult=n_mult, dir1=dir1, jitter=jitter, dir2=dir2, raw_noise=noise, white_bkgd=args.white_bkgd,
                                          want_rgb=False)
             if world > 1:

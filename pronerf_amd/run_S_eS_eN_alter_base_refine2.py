@@ -352,14 +352,20 @@ def train(argv=None, device='cuda'):
         restore_optimizer(tr, ck, 2)
     adam_steps = [start, 0]
     # rays of all training views, as render() prepares them (:206-279): NDC batch + world-space batch, [n_train*H*W, 11] each
-    with torch.cuda.device(dev):
-        pr = [ops.frame_rays(K, poses[i], H, W, near=0., far=1., device=dev) for i in i_train]
-        rays_all = torch.cat([p[0] for p in pr], 0); or_rays_all = torch.cat([p[1] for p in pr], 0)
-        del pr
-        target_all = torch.as_tensor(images[i_train], dtype=torch.float32).reshape(-1, 3).to(dev)
-        own_all = torch.arange(len(i_train), device=dev).repeat_interleave(H * W)
-        img4, poses_t, K_t, rank = _train_views(images[i_train], poses[i_train], K, dev)
-    n_total = rays_all.shape[0]
+    mode = args.device_batches
+    if mode == 'off':
+        with torch.cuda.device(dev):
+            pr = [ops.frame_rays(K, poses[i], H, W, near=0., far=1., device=dev) for i in i_train]
+            rays_all = torch.cat([p[0] for p in pr], 0); or_rays_all = torch.cat([p[1] for p in pr], 0)
+            del pr
+            target_all = torch.as_tensor(images[i_train], dtype=torch.float32).reshape(-1, 3).to(dev)
+            own_all = torch.arange(len(i_train), device=dev).repeat_interleave(H * W)
+            img4, poses_t, K_t, rank = _train_views(images[i_train], poses[i_train], K, dev)
+        n_total = rays_all.shape[0]
+    else:                                                # the training set stays 17 views and 17 poses: every batch is derived from its ray indices (ops.TrainSet)
+        with torch.cuda.device(dev):
+            tset = ops.TrainSet(ops.Scene.from_views(poses[i_train], images[i_train], K, device=dev), n_local, near=0., far=1.)
+        n_total = len(i_train) * H * W
     epoch = 0
     perm = shared_permutation(n_total, epoch, dev) if world > 1 else torch.randperm(n_total, device=dev)       # :796-799
     i_batch, global_step, log = 0, start, []
@@ -377,13 +383,24 @@ def train(argv=None, device='cuda'):
             continue
         idx = idx[replica * n_local:(replica + 1) * n_local]                                                          # this replica's share
         # the per-batch draws of render_rays (:594-600, :649-661, raw2outputs :497)
-        order = torch.as_tensor(sorted(random.sample(range(nv - 1), 4)), device=dev)
-        ref_nos = rank[own_all[idx]][:, 1:][:, order].contiguous()
-        jitter = torch.abs(torch.normal(0.0, 1.0, size=(idx.shape[0], 8), device=dev) / 5).clamp(max=1 - 2e-6)
-        jdir = 1 if random.random() > 0.5 else -1
-        noise = torch.randn(idx.shape[0], 8, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
-        loss, _ = tr.fwd_bwd(rays_all[idx], or_rays_all[idx], target_all[idx], img4, poses_t, K_t, ref_nos, jitter=jitter, jitter_dir=jdir,
-                             raw_noise=noise, white_bkgd=args.white_bkgd, a_mmrgb=args.a_mmrgb, want_rgb=False)
+        if mode == 'off':
+            order = torch.as_tensor(sorted(random.sample(range(nv - 1), 4)), device=dev)
+            ref_nos = rank[own_all[idx]][:, 1:][:, order].contiguous()
+            jitter = torch.abs(torch.normal(0.0, 1.0, size=(idx.shape[0], 8), device=dev) / 5).clamp(max=1 - 2e-6)
+            jdir = 1 if random.random() > 0.5 else -1
+            noise = torch.randn(idx.shape[0], 8, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
+            head = (rays_all[idx], or_rays_all[idx], target_all[idx], img4, poses_t, K_t, ref_nos)
+        elif mode == 'rays':                             # the same draws in the same order; the neighbour ranks travel as four ints in the kernel arguments
+            head = tset.batch(idx, sorted(random.sample(range(nv - 1), 4)))
+            jitter = torch.abs(torch.normal(0.0, 1.0, size=(idx.shape[0], 8), device=dev) / 5).clamp(max=1 - 2e-6)
+            jdir = 1 if random.random() > 0.5 else -1
+            noise = torch.randn(idx.shape[0], 8, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
+        else:                                            # 'all': jitter and noise from the device generator, a function of (batch_seed, iteration, batch row)
+            out = tset.batch(idx, sorted(random.sample(range(nv - 1), 4)), step=i, seed=args.batch_seed, row0=replica * n_local, jitter_cols=8,
+                             jitter_cap=1 - 2e-6, noise_cols=8 if args.raw_noise_std > 0 else 0, noise_std=args.raw_noise_std)
+            head, jitter, noise = out[:7], out[7], (out[8] if args.raw_noise_std > 0 else None)
+            jdir = 1 if random.random() > 0.5 else -1
+        loss, _ = tr.fwd_bwd(*head, jitter=jitter, jitter_dir=jdir, raw_noise=noise, white_bkgd=args.white_bkgd, a_mmrgb=args.a_mmrgb, want_rgb=False)
         if world > 1:
             from .dist import allreduce_gradients
             allreduce_gradients(tr)
