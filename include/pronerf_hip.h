@@ -60,7 +60,15 @@ const char* pnrf_last_error(void);
  *   PNRF_NET_NERF     63 -> (D - 1) x 256 (ReLU) -> [256 + 27] -> 4     DoNeRFTRT, 3 <= netdepth D <= 8 (from 9 on the reference's skip='auto' moves the
  *                                                                        view input into a hidden layer, run_nerf_helpers.py:1190-1201)
  *   PNRF_NET_NERFCLS  the NeRF class with D = 8, skips = [4], use_viewdirs (12 Linear layers: pts0..7, feature, alpha, views, rgb)
- * No skip connections inside the sampler / refine stacks (mmnetskips beyond the depth, as in the Fern configs).  Everything else returns PNRF_E_SHAPE and
+ * Skip connections inside the sampler / refine stacks (--mmnetskips; the reference's default is [4], the Fern configs put it beyond the depth): behind
+ * backbone layer i of the set the net input is concatenated back, h = cat([x, h]), so Linear i + 1 has in_dim = 256 + in_dim[0].  pnrf_mlp_pack
+ * recognises such a layer by that width for 1 <= i + 1 <= D - 1, i.e. skips in 0 .. D - 2 (a skip at D - 1 would feed the output layer: refused, the
+ * reference cannot run it either); pnrf_mlp_skips reports the set as a mask (bit i = skip behind backbone layer i).  A handle with skips runs the
+ * default kernels, PNRF_VARIANT_SAMPLER_SPLIT and PNRF_VARIANT_SAMPLER_F32 (pnrf_sampler_fwd[_ws], pnrf_refine_fwd, pnrf_refine_project_fwd,
+ * pnrf_mlp_fwd on a refine handle, pnrf_render_rays_fwd); PNRF_VARIANT_REFINE_16X16, PNRF_VARIANT_BF16 on refine, PNRF_VARIANT_SAMPLER_F32_FULL,
+ * pnrf_mlp_fwd on a sampler handle and pnrf_refine_train_fwd return PNRF_E_SHAPE with a message that names skips.  The refine stage's PNRF_SHAPE_WIDE form with
+ * skips is built for num_neighbor <= 4 (its parked net input must fit the LDS beside the ring): pnrf_mlp_set_shape(WIDE) on another skip net returns
+ * PNRF_E_SHAPE, PNRF_SHAPE_AUTO runs it NARROW; a skip refine net with 32 layers and 7 or 8 views is refused by pnrf_mlp_pack.  Everything else returns PNRF_E_SHAPE and
  * the message lists this set.  Three things exist for the Fern values only and say so: the sampler's UNFOLDED first layer (pnrf_mlp_fwd on a sampler handle,
  * PNRF_VARIANT_SAMPLER_F32_FULL: P = 48), PNRF_VARIANT_BF16_32X32 and pnrf_mlp_fwd on a DoNeRFTRT handle (netdepth 8), the training entry points (the
  * trainer's shapes).  pnrf_mlp_kind reports in_dim, from which P = in_dim / 6 resp. nb = (in_dim - 48) / 24 follow. */
@@ -77,10 +85,12 @@ int pnrf_mlp_free(pnrf_mlp_t* h);
  * is written to HOST memory (synchronous device read).  deserialize builds a new handle on the
  * current device from a HOST image; images from another library build (ABI version / stream layout
  * tag), truncated or corrupt images are refused with PNRF_E_STATE / PNRF_E_ARG.
- * pnrf_mlp_kind reports what a handle holds (any out pointer may be NULL). */
+ * pnrf_mlp_kind reports what a handle holds (any out pointer may be NULL); pnrf_mlp_skips the skip mask of a sampler / refine handle (0 for the
+ * other kinds).  Engine images are format 6 since they carry that mask; older images are refused like any other build's. */
 int pnrf_mlp_serialize(const pnrf_mlp_t* h, void* buf, int64_t capacity, int64_t* size);
 int pnrf_mlp_deserialize(const void* buf, int64_t size, pnrf_mlp_t** out);
 int pnrf_mlp_kind(const pnrf_mlp_t* h, int* net, int* in_dim, int* in_dim_x, int* out_dim);
+int pnrf_mlp_skips(const pnrf_mlp_t* h, uint32_t* mask);
 
 /* Kernel variant of a packed network.  PNRF_VARIANT_DEFAULT is what pack / deserialize produce and what every product path runs:
  * sampler with the folded first layer in split fp16 (fp32-grade, three v_mfma_f32_16x16x32_f16 per product) — through pnrf_sampler_fwd_ws /

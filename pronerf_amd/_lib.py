@@ -35,6 +35,7 @@ SIGNATURES = {
     'pnrf_mlp_serialize': (_i, [_p, _p, _i64, C.POINTER(_i64)]),
     'pnrf_mlp_deserialize': (_i, [_p, _i64, C.POINTER(_p)]),
     'pnrf_mlp_kind': (_i, [_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'pnrf_mlp_skips': (_i, [_p, C.POINTER(C.c_uint32)]),
     'pnrf_mlp_set_variant': (_i, [_p, _i]),
     'pnrf_mlp_set_shape': (_i, [_p, _i]),
     'pnrf_mlp_fwd': (_i, [_p, _p, _p, _p, _i64, _i, _p]),

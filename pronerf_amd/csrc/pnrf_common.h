@@ -75,6 +75,7 @@ struct pnrf_mlp {
   int nhid;              // hidden 256 -> 256 layers behind layer 0: sampler / refine mmnetdepth - 1 (Fern: 5), DoNeRFTRT netdepth - 2 (Fern: 6); class net: 0 (fixed structure)
   int nb;                // refine: neighbour views (num_neighbor, 1 .. 8; Fern: 4); other nets: 0
   int npts;              // sampler: ray points of the encoding (N_point_ray_enc; Fern: 48); other nets: 0
+  uint32_t skips;        // sampler / refine: bit i = skip connection behind backbone layer i (mmnetskips): hidden layer i of the kernels reads cat([x, h]); others: 0
   int device;
   int variant;           // PNRF_VARIANT_* (pnrf_mlp_set_variant); 0 = default kernels
   int shape;             // workgroup shape of the fused stages (pnrf_mlp_set_shape): PNRF_SHAPE_AUTO = per launch from the column count, or one forced

@@ -240,11 +240,12 @@ constexpr int BF16_PIECES = 2;
 // F16 = true: the same loop on v_mfma_f32_32x32x16_f16 (fragments and B operands are f16x8): pass 1 of the two-pass sampler.
 __device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma_32x32x16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-template <int NCB, int KS, int NT, int POS0, int PIECES = BF16_PIECES, bool F16 = false, class ST, class BFn, class Epi1, class Pre1>
+// QD: depth of the A-fragment queue (8; the skip forms of the refine / pass-1 kernels, which hold more operands, run a shorter one)
+template <int NCB, int KS, int NT, int POS0, int PIECES = BF16_PIECES, bool F16 = false, int QD = 8, class ST, class BFn, class Epi1, class Pre1>
 __device__ __forceinline__ void layer_bf16(ST& st, const char* ringlane, const float* biaslane, BFn Bi, Epi1 epi1, Pre1 pre1,
                                            f32x16 (&last)[NCB]) {
   constexpr int NF = KS * NT;
-  constexpr int AHEAD = KS < 8 ? KS : 8;
+  constexpr int AHEAD = KS < QD ? KS : QD;
   using frag_t = typename std::conditional<F16, f16x8, bf16x8>::type;
   auto frag_ptr = [&](int g) {
     return (const frag_t*)(ringlane + ((POS0 + g / SLOT_FRAGS) % ST::RING_SLOTS) * SLOT_BYTES + (g % SLOT_FRAGS) * FRAG_BYTES);

@@ -117,24 +117,61 @@ struct RefineL0 {
 };
 static_assert(RefineL0<2>::KS0 == R_KS0 && RefineL0<2>::POS_H == R_POS_H && RefineL0<2>::POS_LAST == R_POS_LAST && RefineL0<2>::SLOTS_PAD == R_SLOTS_PAD, "NV = 2 is the Fern stream");
 __host__ __device__ constexpr int refine_nv(int nb) { return (nb + 1) / 2; }
-__host__ __device__ constexpr int refine_slots(int nhid, int nv) {
-  const int used = (((3 * nv + 3) * NT_HID + SLOT_FRAGS - 1) / SLOT_FRAGS) + nhid * SLOTS_HID + R_SLOTS_LAST;
+// stream sizes / bias counts as functions of the hidden-layer count (the constants above are the Fern values)
+__host__ __device__ constexpr int pad_slots(int used) { return used + (NSLOTS - used % NSLOTS) % NSLOTS; }
+// Skip connections inside the sampler / refine stacks (mmnetskips; run_nerf_helpers.py:1473-1540 of the reference): after backbone layer i in the set
+// the net input is concatenated back, h = cat([x, h]), so Linear i + 1 — hidden layer l = i of the kernels, bit i of the 32-bit mask — has 256 + in_ch
+// input columns.  Such a layer is a hidden layer plus the k-steps of layer 0 IN THE SAME STREAM'S layer-0 form, added to every output tile
+// (fragment order per tile = consumption order: hidden k-steps, then the x k-steps), and its slots are rounded up to a whole turn of the ring (the tail is zero padding
+// the kernels step over), so that the ring position of every later layer stays the template constant it is without skips:
+//   exact fp32 (folded)   16 tiles x (16 + 1) fragments           = 17 slots -> 20
+//   split fp16            8 pairs x (8 + 1) k-steps x 4 fragments  = 18 slots -> 20
+//   pass 1                8 tiles x (16 + 3, see P1_KS_X)          = 10 slots -> 12
+//   refine                8 tiles x (16 + 3 NV + 3) fragments      = 11 / 13 / 14 / 16 slots -> 12 / 16 / 16 / 16
+// With mask 0 every function below returns what it returned before skips existed.
+__host__ __device__ constexpr int skip_count(uint32_t mask) { return __builtin_popcount(mask); }
+__host__ __device__ constexpr bool skip_mask_ok(uint32_t mask, int nhid) { return nhid >= 32 || (mask >> nhid) == 0; }      // skips in 0 .. D - 2 = nhid - 1
+constexpr int SF_SLOTS_SKIP_USED = layer_slots_f32<S_KS4_H + SF_KS4_0, NT16_HID>();       // 17
+constexpr int SF_SLOTS_SKIP = pad_slots(SF_SLOTS_SKIP_USED);                              // 20
+constexpr int SH_SLOTS_SKIP_USED = layer_slots_h16x2<SH_KS_H + 1, SH_NTP_H>();            // 18
+constexpr int SH_SLOTS_SKIP = pad_slots(SH_SLOTS_SKIP_USED);                              // 20
+// Pass 1 forms layer 0's split product W_hi P_hi + (W_hi P_lo' + W_lo' P_hi) / 2^11 (primes: planes stored x 2^11) on the x-columns of a skip layer with
+// plain MFMAs into the tile's one accumulator: the WHOLE skip layer runs at scale 2^11 — its h-column fragments, its bias row and a first x fragment
+// W_hi 2^11 are stored times 2^11 (a power of two: the same fp16 significands, the same fp32 roundings), the two cross fragments W_hi and W_lo' as in layer
+// 0 — and the deferred epilogue multiplies the accumulator by 2^-11 in front of the ELU.  Three x fragments per tile, B operands P_hi, P_lo', P_hi.
+constexpr int P1_KS_X = 3;
+constexpr float P1_SKIP_SCALE = 2048.f;                                                   // = H16_LO_SCALE
+constexpr int P1_SLOTS_SKIP_USED = layer_slots_bf16<W_HID / 16 + P1_KS_X, NT_HID>();      // 10
+constexpr int P1_SLOTS_SKIP = pad_slots(P1_SLOTS_SKIP_USED);                              // 12
+__host__ __device__ constexpr int refine_skip_slots_used(int nv) { return ((KS_HID + 3 * nv + 3) * NT_HID + SLOT_FRAGS - 1) / SLOT_FRAGS; }
+__host__ __device__ constexpr int refine_skip_slots(int nv) { return pad_slots(refine_skip_slots_used(nv)); }
+// LDS of refine_skip_kernel: ring, bias table (16-byte aligned) and 3 nv + 3 KiB per wave for the parked layer-0 operand; 0 = does not fit a CU's 160 KiB
+// (with the launch's rounding of the dynamic-LDS attribute).  nw = 8 (WIDE) fits only with nv <= 2 (num_neighbor <= 4) and, at nv = 2, up to 18 hidden layers;
+// nw = 4 (NARROW) fits everything but 31 hidden layers with nv = 4.  The packer refuses a skip net whose NARROW form does not fit; pnrf_mlp_set_shape
+// refuses PNRF_SHAPE_WIDE on one whose WIDE form does not; PNRF_SHAPE_AUTO launches such a net NARROW at every size.
+__host__ __device__ constexpr size_t refine_skip_lds(int nhid, int nw, int nv) {
+  const size_t lds = (size_t)NSLOTS * SLOT_BYTES + ((((size_t)(1 + nhid) * W_HID + 32 * R_NT_LAST) * 4 + 15) & ~(size_t)15) + (size_t)nw * (3 * nv + 3) * FRAG_BYTES;
+  return ((lds + 8191) & ~(size_t)4095) <= (size_t)160 * 1024 ? lds : 0;
+}
+static_assert(refine_skip_lds(18, 8, 2) && !refine_skip_lds(19, 8, 2) && !refine_skip_lds(1, 8, 3) && !refine_skip_lds(31, 4, 4) && refine_skip_lds(30, 4, 4) && refine_skip_lds(31, 4, 3), "what fits");
+__host__ __device__ constexpr int refine_slots(int nhid, int nv, uint32_t mask = 0) {
+  const int used = (((3 * nv + 3) * NT_HID + SLOT_FRAGS - 1) / SLOT_FRAGS) + nhid * SLOTS_HID + skip_count(mask) * (refine_skip_slots(nv) - SLOTS_HID) + R_SLOTS_LAST;
   return used + (NSLOTS - used % NSLOTS) % NSLOTS;
 }
 static_assert(refine_slots(R_NHID, 2) == R_NSLOTS, "refine_slots");
-// stream sizes / bias counts as functions of the hidden-layer count (the constants above are the Fern values)
-__host__ __device__ constexpr int pad_slots(int used) { return used + (NSLOTS - used % NSLOTS) % NSLOTS; }
-__host__ __device__ constexpr int s_nslots(int nhid) { return pad_slots(S_SLOTS_L0 + nhid * S_SLOTS_H + S_SLOTS_LAST); }
-__host__ __device__ constexpr int sf_nslots(int nhid) { return pad_slots(SF_SLOTS_L0 + nhid * S_SLOTS_H + S_SLOTS_LAST); }
-__host__ __device__ constexpr int sh_nslots(int nhid) { return pad_slots(SH_SLOTS_L0 + nhid * SH_SLOTS_H + SH_SLOTS_LAST); }
-__host__ __device__ constexpr int p1_slots_used(int nhid) { return P1_SLOTS_L0 + nhid * P1_SLOTS_H + P1_SLOTS_LAST; }
-__host__ __device__ constexpr int p1_nslots(int nhid) { return pad_slots(p1_slots_used(nhid)); }
+__host__ __device__ constexpr int s_nslots(int nhid) { return pad_slots(S_SLOTS_L0 + nhid * S_SLOTS_H + S_SLOTS_LAST); }      // (the unfolded stream: no skips)
+__host__ __device__ constexpr int sf_nslots(int nhid, uint32_t mask = 0) { return pad_slots(SF_SLOTS_L0 + nhid * S_SLOTS_H + skip_count(mask) * (SF_SLOTS_SKIP - S_SLOTS_H) + S_SLOTS_LAST); }
+__host__ __device__ constexpr int sh_nslots(int nhid, uint32_t mask = 0) { return pad_slots(SH_SLOTS_L0 + nhid * SH_SLOTS_H + skip_count(mask) * (SH_SLOTS_SKIP - SH_SLOTS_H) + SH_SLOTS_LAST); }
+__host__ __device__ constexpr int p1_slots_used(int nhid, uint32_t mask = 0) { return P1_SLOTS_L0 + nhid * P1_SLOTS_H + skip_count(mask) * (P1_SLOTS_SKIP - P1_SLOTS_H) + P1_SLOTS_LAST; }
+__host__ __device__ constexpr int p1_nslots(int nhid, uint32_t mask = 0) { return pad_slots(p1_slots_used(nhid, mask)); }
 __host__ __device__ constexpr int p1_nconst(int nhid) { return 1 + nhid < P1_NCONST ? P1_NCONST : 1 + nhid; }      // [0] output layer, [1 + l] hidden layer l
 __host__ __device__ constexpr int s_nbias(int nhid) { return (1 + nhid) * W_HID + 16 * S_NT_LAST; }
 __host__ __device__ constexpr int p1_nbias(int nhid) { return (1 + nhid) * W_HID + 32; }
 __host__ __device__ constexpr int r_nbias(int nhid) { return (1 + nhid) * W_HID + 32 * R_NT_LAST; }
 static_assert(s_nslots(S_NHID) == S_NSLOTS && sf_nslots(S_NHID) == SF_NSLOTS && sh_nslots(S_NHID) == SH_NSLOTS && p1_nslots(S_NHID) == P1_NSLOTS &&
               s_nbias(S_NHID) == S_NBIAS && p1_nbias(S_NHID) == P1_NBIAS && r_nbias(R_NHID) == R_NBIAS, "Fern values");
+static_assert(SF_SLOTS_SKIP % NSLOTS == 0 && SH_SLOTS_SKIP % NSLOTS == 0 && P1_SLOTS_SKIP % NSLOTS == 0 && refine_skip_slots(1) % NSLOTS == 0 && refine_skip_slots(4) % NSLOTS == 0,
+              "a skip layer must keep the ring position static");
 
 // ---- refine on the 16x16x32 engine (layer_e16, fp16 operands; refine16_kernel, round 6): 32-deep k-steps, 16-row tiles in pairs, two 16-column blocks
 // per wave.  Lane l: ray l & 15 of each block, group g = l >> 4.  A lane group holds NV4 = ceil(nb / 4) neighbour views x 8 samples x 3 colours, then

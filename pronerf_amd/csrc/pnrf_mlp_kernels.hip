@@ -157,6 +157,7 @@ __device__ __forceinline__ void moment(float ox, float oy, float oz, float dx, f
 struct SamplerArgs {
   const void* blob; const float* bias; uint32_t nslots; int nbias;
   int nhid;                                        // hidden 256 -> 256 layers behind layer 0 (mmnetdepth - 1; the Fern configs: 5)
+  uint32_t skips;                                  // the *_skip_kernel forms: bit l = hidden layer l reads cat([x, h]) (pnrf_layout.h); wave-uniform.  (In what was padding.)
   int64_t n; int nbatch;
   const float* rays; const float* tvals;           // fused producer
   const float* x; const int* in0;                  // module-level producer
@@ -196,8 +197,11 @@ __device__ __forceinline__ float sel4(int q, float a, float b, float c, float d)
 
 // MODE 0: module-level (x -> y); 1: fused, full K=288 first layer; 2: fused, folded 6->256 first layer.
 // 8 waves x 16 columns = 128 rays per workgroup batch, two waves per SIMD.
-template <int MODE>
-__global__ __launch_bounds__(512, 2) void sampler_kernel(SamplerArgs a) {
+// SKIPS (sampler_skip_kernel: MODE 2 only): a hidden layer whose bit is set in a.skips carries one more fragment per tile, the folded input's four
+// k-steps, whose B operand is layer 0's B0 — the same exact-fp32 MFMA chain into the same accumulators — and steps over its stream padding.
+template <int MODE, bool SKIPS>
+__device__ __forceinline__ void sampler_body(const SamplerArgs a) {
+  static_assert(!SKIPS || MODE == 2, "skip layers exist in the folded stream");
   constexpr bool FUSED = MODE != 0;
   constexpr int TPB = 512, NW = 8;
   // pass 3 of the sampler (MODE 2 with a list): the rays whose fp16 activations saturated in the split kernel.  Almost always none: leave
@@ -271,6 +275,18 @@ __global__ __launch_bounds__(512, 2) void sampler_kernel(SamplerArgs a) {
     f32x4 X[NT16_HID], Y[NT16_HID], pend;
     auto hidden = [&](f32x4(&in)[NT16_HID], f32x4(&out)[NT16_HID], int l) {
       f32x4 np;
+      if constexpr (SKIPS) {
+        if ((a.skips >> l) & 1u) {
+          layer_f32<S_KS4_H + KS4_0, NT16_HID, POS_H>(
+              st, ringlane, biaslane + (1 + l) * W_HID, [&](int kk) { return kk < W_HID / 4 ? in[(kk >> 2) % NT16_HID][kk & 3] : B0[kk % KS0]; },
+              [&](int to, int r, float v) { out[to][r] = act_f32(v, ACT_ELU); },
+              [&](int r) { in[NT16_HID - 1][r] = act_f32(pend[r], ACT_ELU); }, np);
+          pend = np;
+#pragma unroll
+          for (int i = 0; i < SF_SLOTS_SKIP - SF_SLOTS_SKIP_USED; ++i) st.begin();
+          return;
+        }
+      }
       layer_f32<S_KS4_H, NT16_HID, POS_H>(
           st, ringlane, biaslane + (1 + l) * W_HID, [&](int kk) { return in[kk >> 2][kk & 3]; },
           [&](int to, int r, float v) { out[to][r] = act_f32(v, ACT_ELU); },
@@ -365,6 +381,9 @@ __global__ __launch_bounds__(512, 2) void sampler_kernel(SamplerArgs a) {
     if (atomicAdd(a.counters + 4, 1) == (int)gridDim.x - 1) { a.counters[3] = 0; a.counters[4] = 0; }
   }
 }
+template <int MODE>
+__global__ __launch_bounds__(512, 2) void sampler_kernel(SamplerArgs a) { sampler_body<MODE, false>(a); }
+__global__ __launch_bounds__(512, 2) void sampler_skip_kernel(SamplerArgs a) { sampler_body<2, true>(a); }
 
 // Sampler in split fp16 (layer_h16x2): same producer geometry (16 columns per wave, lane quarter q), same fused epilogue;
 // the hidden activations live as two fp16 planes per 32-feature k-step (hi, lo*2^11).  Fused path, folded first layer only.
@@ -380,9 +399,13 @@ __device__ __forceinline__ void split_h16(const float (&v)[8], f16x8& hi, f16x8&
 // NW = 8: 128 rays per workgroup batch, two waves per SIMD.  NW = 4: 64 rays per batch, a SIMD per wave: the same instruction stream per
 // wave — results are bit-identical — at half the batch latency, for calls with at most one batch per CU (ray chunks, the short list of pass 2).
 // One workgroup per CU in both shapes (stage_shape).
-template <int NW>
-__global__ __launch_bounds__(64 * NW, 2) void sampler_h16_kernel(SamplerArgs a) {
+// SKIPS (sampler_h16_skip_kernel): a hidden layer whose bit is set in a.skips runs a ninth k-step per tile pair on layer 0's operand P0h / P0l — the
+// same three-MFMA split product into the same accumulators — and steps over its stream padding.
+template <int NW, bool SKIPS>
+__device__ __forceinline__ void sampler_h16_body(const SamplerArgs a) {
   constexpr int TPB = 64 * NW;
+  // the skip form keeps layer 0's operand (8 registers) through the hidden layers: its A-fragment queue is two fragments shorter to make room
+  constexpr int HQ = SKIPS ? PNRF_H16_AHEAD - 2 : PNRF_H16_AHEAD;
   PrecF16::enter();               // packed activations saturate at +-65 504 instead of overflowing to inf (see PrecF16)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* bias_lds = (float*)(smem + RING_BYTES);
@@ -461,10 +484,24 @@ __global__ __launch_bounds__(64 * NW, 2) void sampler_h16_kernel(SamplerArgs a) 
     };
     auto hidden = [&](f16x8(&ih)[SH_KS_H], f16x8(&il)[SH_KS_H], f16x8(&oh)[SH_KS_H], f16x8(&ol)[SH_KS_H], int l) {
       f32x4 nm[2], nc[2];
-      layer_h16x2<SH_KS_H, SH_NTP_H, SH_POS_H>(
-          st, ringlane, biaslane + (1 + l) * W_HID, [&](int ks, int pl) { return pl == 0 ? ih[ks] : il[ks]; },
-          [&](int tp, int pcx, f32x4(&mn)[2], f32x4(&cr)[2]) { store_piece(oh, ol, tp, pcx, mn, cr); },
-          [&](int pcx) { store_piece(ih, il, SH_NTP_H - 1, pcx, pm, pc); }, nm, nc);
+      bool done = false;
+      if constexpr (SKIPS) {
+        if ((a.skips >> l) & 1u) {
+          layer_h16x2<SH_KS_H + 1, SH_NTP_H, SH_POS_H, HQ>(
+              st, ringlane, biaslane + (1 + l) * W_HID, [&](int ks, int pl) { return ks < SH_KS_H ? (pl == 0 ? ih[ks % SH_KS_H] : il[ks % SH_KS_H]) : (pl == 0 ? P0h : P0l); },
+              [&](int tp, int pcx, f32x4(&mn)[2], f32x4(&cr)[2]) { store_piece(oh, ol, tp, pcx, mn, cr); },
+              [&](int pcx) { store_piece(ih, il, SH_NTP_H - 1, pcx, pm, pc); }, nm, nc);
+#pragma unroll
+          for (int i = 0; i < SH_SLOTS_SKIP - SH_SLOTS_SKIP_USED; ++i) st.begin();
+          done = true;
+        }
+      }
+      if (!done) {
+        layer_h16x2<SH_KS_H, SH_NTP_H, SH_POS_H, HQ>(
+            st, ringlane, biaslane + (1 + l) * W_HID, [&](int ks, int pl) { return pl == 0 ? ih[ks] : il[ks]; },
+            [&](int tp, int pcx, f32x4(&mn)[2], f32x4(&cr)[2]) { store_piece(oh, ol, tp, pcx, mn, cr); },
+            [&](int pcx) { store_piece(ih, il, SH_NTP_H - 1, pcx, pm, pc); }, nm, nc);
+      }
 #pragma unroll
       for (int t = 0; t < 2; ++t) { pm[t] = nm[t]; pc[t] = nc[t]; }
     };
@@ -564,6 +601,10 @@ __global__ __launch_bounds__(64 * NW, 2) void sampler_h16_kernel(SamplerArgs a) 
     if (atomicAdd(a.counters + 2, 1) == (int)gridDim.x - 1) { a.counters[0] = 0; a.counters[2] = 0; }
   }
 }
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void sampler_h16_kernel(SamplerArgs a) { sampler_h16_body<NW, false>(a); }
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void sampler_h16_skip_kernel(SamplerArgs a) { sampler_h16_body<NW, true>(a); }
 
 // ------------------------------------------------------------------------------------------ sampler, pass 1 of two
 // The sampler's outputs are SORTED, so its products must be fp32-grade wherever two of a ray's eight depths are close — and only there.
@@ -581,11 +622,13 @@ __device__ __forceinline__ int cvt_pk_f16(float a, float b) {        // one v_cv
   return pk;
 }
 // deferred hidden-layer epilogue of pass 1, one activation per piece (as HiddenEpi<.., 16>): ELU on the log2(e) scale, |x|^2, fp16 pack
-struct P1Epi {
+// SCALED (tiles of a skip layer, in the skip form): the accumulators arrive times 2^11 (pnrf_layout.h, P1_KS_X)
+template <bool SCALED>
+struct P1EpiT {
   f16x8 (&Bn)[KS_HID];
   float& ssq;
   __device__ __forceinline__ void operator()(int to, int pc, f32x16 (&acc)[1]) const {
-    const float v = elu_scaled(acc[0][pc]);
+    const float v = elu_scaled(SCALED ? acc[0][pc] * (1.f / P1_SKIP_SCALE) : acc[0][pc]);
     acc[0][pc] = v;
     ssq = fmaf(v, v, ssq);
     if (pc & 1) {
@@ -596,9 +639,14 @@ struct P1Epi {
     }
   }
 };
+using P1Epi = P1EpiT<false>;
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW, 2) void sampler_p1_kernel(SamplerArgs a) {
+// SKIPS (sampler_p1_skip_kernel): a hidden layer whose bit is set in a.skips carries, behind the 16 plain fp16 k-steps of every tile, three fragments that
+// form layer 0's split product on the folded input, W_hi P_hi + (W_hi P_lo + W_lo P_hi) / 2^11 — fp32-grade like layer 0, so the x-part adds no
+// first-order term to the error model (C_l and |x_l|^2 stay those of the h-columns: DESIGN.md 4.1) — as three plain MFMAs into the tile's accumulator:
+// the layer runs at scale 2^11 and its epilogue scales back (pnrf_layout.h, P1_KS_X).  Layer 0's operand stays in registers; the A-fragment queue is shorter.
+template <int NW, bool SKIPS>
+__device__ __forceinline__ void sampler_p1_body(const SamplerArgs a) {
   constexpr int TPB = 64 * NW;
   PrecF16::enter();
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -640,6 +688,7 @@ __global__ __launch_bounds__(64 * NW, 2) void sampler_p1_kernel(SamplerArgs a) {
     // its gaps (its pass-1 values are wrong; the split kernel and, if that saturates too, the exact-fp32 kernel render it)
     constexpr float OVF2 = 65504.f * 65504.f;
     bool ovf = false;
+    constexpr int P1Q = 4;                   // A-fragment queue of the skip form's hidden layers (8 in the plain kernel; what fits without spills)
 
     // ---- layer 0: 8 tiles x (W_hi P_hi | W_hi P_lo + W_lo P_hi), one slot; tile t's activation runs behind tile t+1's MFMAs
     {
@@ -673,8 +722,23 @@ __global__ __launch_bounds__(64 * NW, 2) void sampler_p1_kernel(SamplerArgs a) {
     // |x_l|^2 is complete when layer l's call returns: fold it into V there and hand the accumulator to layer l+1's outputs
     auto hidden = [&](f16x8(&in)[KS_HID], f16x8(&out)[KS_HID], int l, float& sq_in, float& sq_out) {
       f32x16 np[1];
-      layer_bf16<1, KS_HID, NT_HID, P1_POS_H, 16, true>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int, int ks) { return in[ks]; }, P1Epi{out, sq_out},
-                                                         [&](int pc) { P1Epi{in, sq_in}(NT_HID - 1, pc, pend); }, np);
+      if constexpr (SKIPS) {
+        if ((a.skips >> l) & 1u) {
+          layer_bf16<1, KS_HID + P1_KS_X, NT_HID, P1_POS_H, 16, true, P1Q>(
+              st, ringlane, biaslane + (1 + l) * W_HID, [&](int, int ks) { return ks < KS_HID ? in[ks % KS_HID] : (ks == KS_HID + 1 ? P0l : P0h); }, P1EpiT<true>{out, sq_out},
+              [&](int pc) { P1Epi{in, sq_in}(NT_HID - 1, pc, pend); }, np);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) np[0][i] *= 1.f / P1_SKIP_SCALE;      // the last tile leaves at true scale: whoever activates it need not know
+#pragma unroll
+          for (int i = 0; i < P1_SLOTS_SKIP - P1_SLOTS_SKIP_USED; ++i) st.begin();
+        } else {
+          layer_bf16<1, KS_HID, NT_HID, P1_POS_H, 16, true, P1Q>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int, int ks) { return in[ks]; }, P1Epi{out, sq_out},
+                                                                  [&](int pc) { P1Epi{in, sq_in}(NT_HID - 1, pc, pend); }, np);
+        }
+      } else {
+        layer_bf16<1, KS_HID, NT_HID, P1_POS_H, 16, true>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int, int ks) { return in[ks]; }, P1Epi{out, sq_out},
+                                                           [&](int pc) { P1Epi{in, sq_in}(NT_HID - 1, pc, pend); }, np);
+      }
       pend[0] = np[0];
       ovf |= sq_in >= OVF2;
       V = a.p1c[1 + l] * fmaf(C2, sq_in, V);
@@ -793,6 +857,10 @@ __global__ __launch_bounds__(64 * NW, 2) void sampler_p1_kernel(SamplerArgs a) {
   }
   st.drain();
 }
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void sampler_p1_kernel(SamplerArgs a) { sampler_p1_body<NW, false>(a); }
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void sampler_p1_skip_kernel(SamplerArgs a) { sampler_p1_body<NW, true>(a); }
 
 // ------------------------------------------------------------------------------------------ bf16 nets
 // Deferred hidden-layer epilogue, one piece at a time: piece pc = accumulator registers 8pc..8pc+7 of tile
@@ -861,6 +929,7 @@ struct RefineArgs {
   const void* blob; const float* bias; uint32_t nslots; int nbias;
   int nhid, nb;                                     // hidden 256 -> 256 layers behind layer 0 (mmnetdepth - 1; Fern: 5); neighbour views (num_neighbor; Fern: 4)
   int64_t n; int nbatch;
+  uint32_t skips;                                   // refine_skip_kernel: bit l = hidden layer l reads cat([x, h]) (pnrf_layout.h); wave-uniform.  (In what was padding.)
   const float* x;                                   // refine_in [n,144] (HEAD = 0)
   const float* or_rays; const float4* img4; const float* proj; int Hf, Wf; float eps;   // HEAD = 1: the projection runs in the kernel
   const float* rays; const float* depth_sorted;     // fused consumer
@@ -875,8 +944,13 @@ struct RefineArgs {
 // (refine_in0): no [n,144] round trip through HBM, one kernel launch less per frame.
 // NV: neighbour views per lane half = ceil(num_neighbor / 2) (Fern: 2).  A lane half holds 24 NV colour values + 24 Pluecker values = 3 NV + 3
 // k-steps of layer 0 (refine_in0_nv); a view index >= a.nb is padding (zero weights in the stream; its inputs are fetched from the last real view).
-template <int NCB, int NW, int MODE, int HEAD = 0, class P = PrecBf16, int NV = 2>
-__global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(RefineArgs a) {
+// SKIPS (refine_skip_kernel): a hidden layer whose bit is set in a.skips runs, behind the 16 k-steps of every tile, layer 0's KS0 k-steps on the net
+// input.  Layer 0's packed operand has to outlive the ping-pong buffers that overwrite it: every wave parks its KS0 fragments in LDS behind the bias
+// table (KS0 KiB per wave; registers would take 4 KS0 = 24 .. 60 more beside the 230 .. 242 the plain kernel needs: spills at two waves per SIMD) and a
+// skip layer reads them back as B operands through a two-deep register queue filled two k-steps ahead.  Neither the projection nor a texel fetch runs twice.
+template <int NCB, int NW, int MODE, int HEAD, class P, int NV, bool SKIPS>
+__device__ __forceinline__ void refine_body(const RefineArgs a) {
+  static_assert(!SKIPS || (NCB == 1 && MODE != 2), "the skip form exists for the inference stage and the module-level forward");
   constexpr bool FUSED = MODE != 0;
   using RL = RefineL0<NV>;
   constexpr int KS0 = RL::KS0;
@@ -898,6 +972,9 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
   young_half_priority<NW>();
   const char* ringlane = smem + lane * 16;
   const float* biaslane = bias_lds + h * 16;
+  // SKIPS: this wave's parked layer-0 operand, [KS0][64 lanes] fragments behind the bias table (16-byte aligned)
+  char* xlane = nullptr;
+  if constexpr (SKIPS) xlane = smem + RING_BYTES + (((size_t)a.nbias * 4 + 15) & ~(size_t)15) + (size_t)wave * (KS0 * FRAG_BYTES) + lane * 16;
 
   // Batch order.  HEAD = 1 fetches the neighbour images: workgroups b and b + 8 share an XCD (its L2) under the round-robin placement the
   // dispatcher is observed to use, so the workgroups of residue x walk the x-th EIGHTH of the batches — one band of the frame, whose samples
@@ -959,7 +1036,7 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
         // 8 NV projections per lane (view vv = p / 8, sample p % 8) in a software pipeline: the four texel fetches of projection p + D are issued
         // before projection p is blended, so D projections (4 D x 16 B per lane) are in flight.  The fences keep the compiler from hoisting
         // all 64 fetches to the top of the batch (256 registers of texels: it spilled 187).
-        constexpr int D = 4;
+        constexpr int D = (SKIPS && NV > 2) ? 2 : 4;      // (the skip form with 3 / 4 views per lane half: a shallower pipeline, for registers)
         float wt[D][4];
         float4 tx[D][4];
         ViewRay vr[NV];
@@ -1033,6 +1110,10 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
         }
       }
     });
+    if constexpr (SKIPS) {
+#pragma unroll
+      for (int ks = 0; ks < KS0; ++ks) *(v8*)(xlane + ks * FRAG_BYTES) = Bo[0][ks];
+    }
     // ping-pong: layer 0 Bo -> Bn, then Bn -> Bo, Bo -> Bn, ... (5 hidden layers end in Bo);
     // `pend` = raw accumulators of the previous layer's last tile (its epilogue is deferred into the next layer)
     f32x16 pend[NCB];
@@ -1046,8 +1127,35 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
 #endif
     auto hidden = [&](v8(&in)[NCB][KS_HID], v8(&out)[NCB][KS_HID], int l) {
       f32x16 np[NCB];
-      layer_bf16<NCB, KS_HID, NT_HID, RL::POS_H, RP, F16>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int cb, int ks) { return in[cb][ks]; },
-                                                   HiddenEpi<NCB, ACT_ELU, RP, P>{out}, [&](int pc) { HiddenEpi<NCB, ACT_ELU, RP, P>{in}(NT_HID - 1, pc, pend); }, np);
+      if constexpr (SKIPS) {
+        constexpr int RQ = (HEAD == 1 && NV > 2) ? 2 : 4;      // A-fragment queue of the skip form (8 in the plain kernel): room for the x fragments in flight
+        if ((a.skips >> l) & 1u) {
+          constexpr int XQ = 2;                  // x fragments in flight from LDS
+          v8 xq[XQ];
+          auto xfrag = [&](int j) { return *(const v8*)(xlane + j * FRAG_BYTES); };
+          layer_bf16<NCB, KS_HID + KS0, NT_HID, RL::POS_H, RP, F16, RQ>(
+              st, ringlane, biaslane + (1 + l) * W_HID,
+              [&](int cb, int ks) {
+                if (ks < KS_HID) {
+                  if (ks >= KS_HID - XQ) xq[ks - (KS_HID - XQ)] = xfrag(ks - (KS_HID - XQ));      // the last two hidden k-steps of every tile fetch x fragments 0, 1
+                  return in[cb][ks % KS_HID];
+                }
+                const int j = ks - KS_HID;
+                const v8 cur = xq[j % XQ];
+                if (j + XQ < KS0) xq[j % XQ] = xfrag(j + XQ);
+                return cur;
+              },
+              HiddenEpi<NCB, ACT_ELU, RP, P>{out}, [&](int pc) { HiddenEpi<NCB, ACT_ELU, RP, P>{in}(NT_HID - 1, pc, pend); }, np);
+#pragma unroll
+          for (int i = 0; i < refine_skip_slots(NV) - refine_skip_slots_used(NV); ++i) st.begin();
+        } else {
+          layer_bf16<NCB, KS_HID, NT_HID, RL::POS_H, RP, F16, RQ>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int cb, int ks) { return in[cb][ks]; },
+                                                                   HiddenEpi<NCB, ACT_ELU, RP, P>{out}, [&](int pc) { HiddenEpi<NCB, ACT_ELU, RP, P>{in}(NT_HID - 1, pc, pend); }, np);
+        }
+      } else {
+        layer_bf16<NCB, KS_HID, NT_HID, RL::POS_H, RP, F16>(st, ringlane, biaslane + (1 + l) * W_HID, [&](int cb, int ks) { return in[cb][ks]; },
+                                                     HiddenEpi<NCB, ACT_ELU, RP, P>{out}, [&](int pc) { HiddenEpi<NCB, ACT_ELU, RP, P>{in}(NT_HID - 1, pc, pend); }, np);
+      }
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) pend[cb] = np[cb];
 #ifdef PNRF_DEBUG_EHEAD
@@ -1128,7 +1236,19 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
     // ---- fused epilogue: lane (ray, h) owns samples 4h..4h+3: reg 4a = refine logit, 4a+1..3 = offset
     static_for<NCB>([&](auto cbc) {
       constexpr int cb = decltype(cbc)::value;
-      const int64_t rr = valid[cb] ? row[cb] : a.n - 1;
+      // the skip form derives the lane's row and addresses again here: held (or hoisted out of the batch loop) they cost the registers its layers need
+      uint32_t tid = threadIdx.x;
+      if constexpr (SKIPS) asm volatile("" : "+v"(tid));
+      const int h = (tid >> 5) & 1;
+      const int64_t row_e = SKIPS ? (int64_t)batch * (NW * COLS) + (tid >> 6) * COLS + cb * 32 + (tid & 31) : row[cb];
+      const bool valid_e = SKIPS ? row_e < a.n : valid[cb];
+      const int64_t rr = valid_e ? row_e : a.n - 1;
+      if constexpr (SKIPS) {                     // the skip form fetches the epilogue's inputs again here (they are L2-resident) instead of holding
+        const float* rl = a.rays + rr * 11;        // 16 registers through the layers
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e_ray[cb][i] = rl[i];
+        e_d0[cb] = *(const float4*)(a.depth_sorted + rr * 8); e_d1[cb] = *(const float4*)(a.depth_sorted + rr * 8 + 4);
+      }
       const float* r = e_ray[cb];
       const float ox = r[0], oy = r[1], oz = r[2], dx = r[3], dy = r[4], dz = r[5], near = r[6], far = r[7];
       const float4 d0 = e_d0[cb], d1 = e_d1[cb];
@@ -1173,8 +1293,8 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
         pp[3 * s4 + 2] = ieee_add(ieee_add(oz, ieee_mul(dz, zv)), ieee_mul(1e-2f, fz));
       }
 #ifdef PNRF_DEBUG_EHEAD
-      if (MODE == 1 && valid[cb] && g_dbg_ehead) {
-        const int64_t g = (a.rays - g_dbg_rays_base) / 11 + row[cb];
+      if (MODE == 1 && valid_e && g_dbg_ehead) {
+        const int64_t g = (a.rays - g_dbg_rays_base) / 11 + row_e;
         float* d = g_dbg_ehead + (g * 2 + h) * DBG_STRIDE;
         d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
 #pragma unroll
@@ -1190,9 +1310,9 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
         for (int i = 0; i < 16; ++i) d[32 + i] = fin[cb][i];
       }
 #endif
-      if (valid[cb]) {
-        *(float4*)(a.z + row[cb] * 8 + 4 * h) = make_float4(zz[0], zz[1], zz[2], zz[3]);
-        float4* pq = (float4*)(a.pts + row[cb] * 24 + 12 * h);
+      if (valid_e) {
+        *(float4*)(a.z + row_e * 8 + 4 * h) = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        float4* pq = (float4*)(a.pts + row_e * 24 + 12 * h);
         pq[0] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         pq[1] = make_float4(pp[4], pp[5], pp[6], pp[7]);
         pq[2] = make_float4(pp[8], pp[9], pp[10], pp[11]);
@@ -1201,6 +1321,10 @@ __global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(Refin
   }
   st.drain();
 }
+template <int NCB, int NW, int MODE, int HEAD = 0, class P = PrecBf16, int NV = 2>
+__global__ __launch_bounds__(64 * NW, NCB == 1 ? 2 : 1) void refine_kernel(RefineArgs a) { refine_body<NCB, NW, MODE, HEAD, P, NV, false>(a); }
+template <int NW, int MODE, int HEAD, int NV>
+__global__ __launch_bounds__(64 * NW, 2) void refine_skip_kernel(RefineArgs a) { refine_body<1, NW, MODE, HEAD, PrecF16, NV, true>(a); }
 
 // ------------------------------------------------------------------------------------------ refine stage on the 16x16x32 engine (round 6)
 // refine16_kernel: the fused inference refine stage (projection head or refine_in rows -> ELU MLP -> interval refinement + query points) on layer_e16:
@@ -2174,9 +2298,10 @@ size_t narrow_lds(size_t lds) { return lds > NARROW_LDS_BYTES ? lds : NARROW_LDS
 static int sampler_launch(const pnrf_mlp_t* h, const float* rays, int64_t n, float* depth_sorted, float* add_sorted, float* mul_sorted,
                           int64_t* sort_idx, float* mm_rgb, float* depth_raw, void* workspace, bool ws_clean, float kappa, void* stream) {
   SamplerArgs a = {};
-  a.bias = h->d_bias; a.nbias = h->nbias; a.nhid = h->nhid;
+  a.bias = h->d_bias; a.nbias = h->nbias; a.nhid = h->nhid; a.skips = h->skips;
   a.n = n; a.nbatch = (int)((n + 127) / 128);
   a.rays = rays; a.tvals = h->d_tvals;
+  const bool skips = h->skips != 0;            // a net with skip connections runs the *_skip_kernel form of every pass (the plain instances stay what they were)
   a.depth_sorted = depth_sorted; a.add_sorted = add_sorted; a.mul_sorted = mul_sorted;
   a.sort_idx = sort_idx; a.mm_rgb = mm_rgb; a.depth_raw = depth_raw;
   const size_t lds = RING_BYTES + (size_t)h->nbias * 4;
@@ -2188,17 +2313,17 @@ static int sampler_launch(const pnrf_mlp_t* h, const float* rays, int64_t n, flo
   auto launch_h16 = [&](SamplerArgs& x, int64_t rows, int64_t expect) {
     if (stage_shape(h, expect, 16) == SHAPE_NARROW) {
       x.nbatch = (int)((rows + 63) / 64);
-      return launch_mlp(sampler_h16_kernel<4>, x, 256, narrow_lds(lds), x.nbatch, st);
+      return skips ? launch_mlp(sampler_h16_skip_kernel<4>, x, 256, narrow_lds(lds), x.nbatch, st) : launch_mlp(sampler_h16_kernel<4>, x, 256, narrow_lds(lds), x.nbatch, st);
     }
     x.nbatch = (int)((rows + 127) / 128);
-    return launch_mlp(sampler_h16_kernel<8>, x, 512, lds, x.nbatch, st);
+    return skips ? launch_mlp(sampler_h16_skip_kernel<8>, x, 512, lds, x.nbatch, st) : launch_mlp(sampler_h16_kernel<8>, x, 512, lds, x.nbatch, st);
   };
   // pass 3: a few workgroups (the saturated list is empty on every net whose activations stay inside the fp16 range: they leave at once)
   auto launch_f32_list = [&](SamplerArgs& f, int* counters, int* sat_list) {
     f.blob = h->d_blob_fold; f.nslots = h->nslots_fold;
     f.list = sat_list; f.list_count = counters + 3; f.counters = counters; f.sat_list = nullptr;
     const int nb = (int)((n + 127) / 128);
-    return launch_mlp(sampler_kernel<2>, f, 512, lds, nb < 16 ? nb : 16, st);
+    return skips ? launch_mlp(sampler_skip_kernel, f, 512, lds, nb < 16 ? nb : 16, st) : launch_mlp(sampler_kernel<2>, f, 512, lds, nb < 16 ? nb : 16, st);
   };
   void* workspace_split = nullptr;
   if (workspace && h->variant == PNRF_VARIANT_SAMPLER_SPLIT) { workspace_split = workspace; workspace = nullptr; }
@@ -2215,10 +2340,10 @@ static int sampler_launch(const pnrf_mlp_t* h, const float* rays, int64_t n, flo
     int rc;
     if (stage_shape(h, n, 32) == SHAPE_NARROW) {
       p.nbatch = (int)((n + 127) / 128);
-      rc = launch_mlp(sampler_p1_kernel<4>, p, 256, narrow_lds(lds1), p.nbatch, st);
+      rc = skips ? launch_mlp(sampler_p1_skip_kernel<4>, p, 256, narrow_lds(lds1), p.nbatch, st) : launch_mlp(sampler_p1_kernel<4>, p, 256, narrow_lds(lds1), p.nbatch, st);
     } else {
       p.nbatch = (int)((n + 255) / 256);
-      rc = launch_mlp(sampler_p1_kernel<8>, p, 512, lds1, p.nbatch, st);
+      rc = skips ? launch_mlp(sampler_p1_skip_kernel<8>, p, 512, lds1, p.nbatch, st) : launch_mlp(sampler_p1_kernel<8>, p, 512, lds1, p.nbatch, st);
     }
     if (rc) return rc;
     SamplerArgs f = a;                                    // pass 3 (exact fp32, folded first layer) on the rays pass 2 reports as saturated
@@ -2240,6 +2365,7 @@ static int sampler_launch(const pnrf_mlp_t* h, const float* rays, int64_t n, flo
     return launch_f32_list(f, counters, counters + 16 + n);
   }
   if (h->variant == PNRF_VARIANT_SAMPLER_F32_FULL) {
+    PNRF_REQUIRE(!skips, PNRF_E_SHAPE, "PNRF_VARIANT_SAMPLER_F32_FULL (the unfolded first layer) is not built for nets with skip connections (mmnetskips)");
     PNRF_REQUIRE(h->npts == S_NPTS && h->d_blob, PNRF_E_SHAPE, "PNRF_VARIANT_SAMPLER_F32_FULL (the unfolded first layer) is built for N_point_ray_enc = %d; this sampler has %d "
                  "(every other variant runs the folded first layer and takes any N_point_ray_enc)", S_NPTS, h->npts);
     a.blob = h->d_blob; a.nslots = h->nslots;
@@ -2247,7 +2373,7 @@ static int sampler_launch(const pnrf_mlp_t* h, const float* rays, int64_t n, flo
   }
   if (h->variant == PNRF_VARIANT_SAMPLER_F32) {
     a.blob = h->d_blob_fold; a.nslots = h->nslots_fold;
-    return launch_mlp(sampler_kernel<2>, a, 512, lds, a.nbatch, st);
+    return skips ? launch_mlp(sampler_skip_kernel, a, 512, lds, a.nbatch, st) : launch_mlp(sampler_kernel<2>, a, 512, lds, a.nbatch, st);
   }
   a.blob = h->d_blob_h16; a.nslots = h->nslots_h16;
   return launch_h16(a, n, n);
@@ -2291,8 +2417,32 @@ extern "C" int pnrf_sampler_fwd_ws(const pnrf_mlp_t* h, const float* rays, int64
 }
 
 // The fused refine stage in its two workgroup shapes (256 / 128 rays per batch; stage_shape) and two operand types
+// A net with skip connections: refine_skip_kernel (fp16 operands; inference stage and module-level forward).  The WIDE shape needs 8 x KS0 KiB of LDS beside
+// the ring (refine_skip_lds, pnrf_layout.h): it is built for num_neighbor <= 4 only and, at 3 or 4 views, fits up to 18 hidden layers.  A net beyond that cannot be forced WIDE
+// (pnrf_mlp_set_shape refuses) and PNRF_SHAPE_AUTO launches it NARROW at every size; one whose NARROW form does not fit is refused by the packer.
+template <int MODE, int HEAD, int NV>
+static int refine_skip_launch_nv(const pnrf_mlp_t* h, RefineArgs& a, int64_t n, hipStream_t st, bool narrow_only) {
+  if constexpr (MODE == 2) {
+    PNRF_REQUIRE(false, PNRF_E_SHAPE, "pnrf_refine_train_fwd is not built for nets with skip connections (mmnetskips; this net's mask: %08x)", h->skips);
+  } else {
+    PNRF_REQUIRE(h->variant == PNRF_VARIANT_DEFAULT, PNRF_E_SHAPE, "variant %d of the refine stage is not built for nets with skip connections (mmnetskips)", h->variant);
+    a.blob = h->d_blob_f16; a.nslots = h->nslots_f16; a.skips = h->skips;
+    const size_t lds8 = NV <= 2 ? refine_skip_lds(h->nhid, 8, NV) : 0, lds4 = refine_skip_lds(h->nhid, 4, NV);
+    PNRF_REQUIRE(lds4 && (lds8 || h->shape != SHAPE_WIDE), PNRF_E_STATE, "refine net with skip connections: handle in a shape its LDS does not allow (packer / pnrf_mlp_set_shape check this)");
+    if (MODE == 0 || narrow_only || !lds8 || stage_shape(h, n, 32) == SHAPE_NARROW) {
+      a.nbatch = (int)((n + 127) / 128);
+      return launch_mlp(refine_skip_kernel<4, MODE, HEAD, NV>, a, 256, narrow_lds(lds4), a.nbatch, st);
+    }
+    if constexpr (MODE == 1 && NV <= 2) {        // (the module-level forward is a narrow launch, as the plain kernel's; no WIDE instance beyond num_neighbor 4)
+      a.nbatch = (int)((n + 255) / 256);
+      return launch_mlp(refine_skip_kernel<8, MODE, HEAD, NV>, a, 512, lds8, a.nbatch, st);
+    }
+  }
+  return 0;
+}
 template <int MODE, int HEAD, int NV>
 static int refine_launch_nv(const pnrf_mlp_t* h, RefineArgs& a, int64_t n, hipStream_t st) {
+  if (h->skips) return refine_skip_launch_nv<MODE, HEAD, NV>(h, a, n, st, false);
   const size_t lds = RING_BYTES + (size_t)h->nbias * 4;
   const bool bf16 = h->variant == PNRF_VARIANT_BF16;
   if constexpr (NV > 2 && HEAD == 1) {          // (its projecting head with 3 / 4 views per lane does not fit the register file beside bf16 packing: it would spill)
@@ -2342,7 +2492,10 @@ template <int MODE, int HEAD>
 static int refine_launch(const pnrf_mlp_t* h, RefineArgs& a, int64_t n, hipStream_t st) {
   a.nhid = h->nhid; a.nb = h->nb;
   if constexpr (MODE == 1) {
-    if (h->variant == PNRF_VARIANT_REFINE_16X16) return refine16_launch<HEAD>(h, a, n, st);
+    if (h->variant == PNRF_VARIANT_REFINE_16X16) {
+      PNRF_REQUIRE(!h->skips, PNRF_E_SHAPE, "PNRF_VARIANT_REFINE_16X16 is not built for nets with skip connections (mmnetskips; this net's mask: %08x)", h->skips);
+      return refine16_launch<HEAD>(h, a, n, st);
+    }
   }
   if constexpr (MODE == 2) {                    // the training-time epilogue belongs to the trainer's shapes
     PNRF_REQUIRE(h->nb == 4, PNRF_E_SHAPE, "pnrf_refine_train_fwd is built for num_neighbor = 4, this refine net has %d", h->nb);
@@ -2503,6 +2656,8 @@ extern "C" int pnrf_mlp_fwd(const pnrf_mlp_t* h, const float* x, const float* x_
   const size_t lds = RING_BYTES + (size_t)h->nbias * 4;
   if (h->net == PNRF_NET_SAMPLER) {
     SamplerArgs a = {};
+    PNRF_REQUIRE(!h->skips, PNRF_E_SHAPE, "pnrf_mlp_fwd: the module-level sampler forward (unfolded first layer) is not built for nets with skip connections (mmnetskips); "
+                 "the fused operators (pnrf_sampler_fwd / pnrf_render_rays_fwd) take them");
     PNRF_REQUIRE(h->npts == S_NPTS && h->d_blob, PNRF_E_SHAPE, "pnrf_mlp_fwd: the module-level sampler forward (unfolded first layer) is built for N_point_ray_enc = %d, "
                  "this sampler has %d; the fused operators (pnrf_sampler_fwd / pnrf_render_rays_fwd) take any", S_NPTS, h->npts);
     a.blob = h->d_blob; a.bias = h->d_bias; a.nslots = h->nslots; a.nbias = h->nbias; a.nhid = h->nhid;
@@ -2521,6 +2676,7 @@ extern "C" int pnrf_mlp_fwd(const pnrf_mlp_t* h, const float* x, const float* x_
     if (!bf16) { a.blob = h->d_blob_f16; a.nslots = h->nslots_f16; }
     auto go = [&](auto nvc) {
       constexpr int NV = decltype(nvc)::value;
+      if (h->skips) return refine_skip_launch_nv<0, 0, NV>(h, a, m, (hipStream_t)stream, true);
       return bf16 ? launch_mlp(refine_kernel<1, 4, 0, 0, PrecBf16, NV>, a, 256, narrow_lds(lds), a.nbatch, (hipStream_t)stream)
                   : launch_mlp(refine_kernel<1, 4, 0, 0, PrecF16, NV>, a, 256, narrow_lds(lds), a.nbatch, (hipStream_t)stream);
     };

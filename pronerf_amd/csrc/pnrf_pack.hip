@@ -36,18 +36,25 @@ struct Layer {
   std::vector<int> out_map;  // bf16: [nt][32], f32: [nt][16]  tile row -> output index or -1
   double wscale = 1.0;       // weights / biases are stored multiplied by these (in double, before the rounding to the stream's type):
   double bscale = 1.0;       // the log2(e) scaling of the ELU nets' streams, see elu_scaled() in pnrf_engine.h
+  int x_from = 1 << 30;      // skip layer (mmnetskips): input columns >= x_from are the net input's (first-layer-like) and carry xscale instead of wscale
+  double xscale = 1.0;
+  int slot_align = 1;        // slots of the layer in a stream are rounded up to a multiple of this (skip layers: NSLOTS, pnrf_layout.h)
 };
-// ELU nets on log2(e)-scaled activations: first layer W, every ELU layer's bias x log2(e); output layer W / log2(e)
+// ELU nets on log2(e)-scaled activations: first layer W, every ELU layer's bias x log2(e); output layer W / log2(e).  The x-columns of a skip layer
+// multiply the unscaled net input like the first layer's and get the factor too; its h-columns multiply scaled activations and do not
 static void scale_for_elu(std::vector<Layer>& Ls) {
-  for (size_t l = 0; l + 1 < Ls.size(); ++l) Ls[l].bscale = LOG2E_D;
+  for (size_t l = 0; l + 1 < Ls.size(); ++l) { Ls[l].bscale = LOG2E_D; Ls[l].xscale = LOG2E_D; }
   Ls.front().wscale = LOG2E_D;
   Ls.back().wscale = 1.0 / LOG2E_D;
 }
 
 static size_t layer_frags(const Layer& L, int prec) { return (size_t)L.nt * (prec == PREC_BF16 ? L.nk : L.nk / 4); }
-static size_t layer_slots(const Layer& L, int prec) { return (layer_frags(L, prec) + SLOT_FRAGS - 1) / SLOT_FRAGS; }
+static size_t align_slots(const Layer& L, size_t slots) { return (slots + L.slot_align - 1) / L.slot_align * L.slot_align; }
+static size_t layer_slots(const Layer& L, int prec) { return align_slots(L, (layer_frags(L, prec) + SLOT_FRAGS - 1) / SLOT_FRAGS); }
 
-static inline float wval(const Layer& L, int out, int in) { return (out >= 0 && in >= 0) ? (float)((double)L.W[(size_t)out * L.in_dim + in] * L.wscale) : 0.f; }
+// weight (out, in) on the stream's scale, in double (0 for padding rows / columns)
+static inline double wdbl(const Layer& L, int out, int in) { return (out >= 0 && in >= 0) ? (double)L.W[(size_t)out * L.in_dim + in] * (in >= L.x_from ? L.xscale : L.wscale) : 0.0; }
+static inline float wval(const Layer& L, int out, int in) { return (float)wdbl(L, out, in); }
 
 static void pack_layer(const Layer& L, int prec, char* dst) {
   if (prec == PREC_BF16) {
@@ -88,8 +95,7 @@ static void pack_layer_h16x2(const Layer& L, char* dst) {
           const int r = lane & 15, g = lane >> 4;
           const int out = L.out_map[(2 * tp + t) * 16 + r];
           for (int j = 0; j < 8; ++j) {
-            const int in = L.in_map[(ks * 4 + g) * 8 + j];
-            const double w = (out >= 0 && in >= 0) ? (double)L.W[(size_t)out * L.in_dim + in] * L.wscale : 0.0;     // split the scaled value itself
+            const double w = wdbl(L, out, L.in_map[(ks * 4 + g) * 8 + j]);     // split the scaled value itself
             const uint16_t h = f2h((float)w);
             hi[lane * 8 + j] = h;
             lo[lane * 8 + j] = f2h((float)((w - (double)h2f(h)) * H16_LO_SCALE));
@@ -110,22 +116,39 @@ static void pack_layer_f16(const Layer& L, char* dst) {
       }
     }
 }
-// ... and its split first layer (one k-step): per tile a W_hi fragment and a W_lo * 2^11 fragment
+// ... and its split first layer (one k-step): per tile a W_hi fragment and a W_lo * 2^11 fragment.  xmap[h * 8 + j] = input column of the k-step
+static void pack_tile_f16x2(const Layer& L, int to, const int* xmap, uint16_t* hi, uint16_t* lo) {
+  for (int lane = 0; lane < 64; ++lane) {
+    const int r = lane & 31, h = lane >> 5;
+    const int out = L.out_map[to * 32 + r];
+    for (int j = 0; j < 8; ++j) {
+      const double w = wdbl(L, out, xmap[h * 8 + j]);
+      const uint16_t hh = f2h((float)w);
+      hi[lane * 8 + j] = hh;
+      lo[lane * 8 + j] = f2h((float)((w - (double)h2f(hh)) * H16_LO_SCALE));
+    }
+  }
+}
 static void pack_layer0_f16x2(const Layer& L, char* dst) {
+  for (int to = 0; to < L.nt; ++to)
+    pack_tile_f16x2(L, to, L.in_map.data(), (uint16_t*)(dst + ((size_t)to * 2 + 0) * FRAG_BYTES), (uint16_t*)(dst + ((size_t)to * 2 + 1) * FRAG_BYTES));
+}
+// ... and a skip layer of that stream (pnrf_layout.h, P1_KS_X): per tile the KS_HID plain fp16 fragments of the h-columns times 2^11, then of the x-columns
+// W_hi 2^11 and the first layer's pair W_hi, W_lo 2^11 (in_map = [KS_HID k-steps of the hidden layer | one k-step of x])
+static void pack_layer_f16_skip(const Layer& L, char* dst) {
+  const int kt = KS_HID + P1_KS_X;
   for (int to = 0; to < L.nt; ++to) {
-    uint16_t* hi = (uint16_t*)(dst + ((size_t)to * 2 + 0) * FRAG_BYTES);
-    uint16_t* lo = (uint16_t*)(dst + ((size_t)to * 2 + 1) * FRAG_BYTES);
-    for (int lane = 0; lane < 64; ++lane) {
-      const int r = lane & 31, h = lane >> 5;
-      const int out = L.out_map[to * 32 + r];
-      for (int j = 0; j < 8; ++j) {
-        const int in = L.in_map[h * 8 + j];
-        const double w = (out >= 0 && in >= 0) ? (double)L.W[(size_t)out * L.in_dim + in] * L.wscale : 0.0;
-        const uint16_t hh = f2h((float)w);
-        hi[lane * 8 + j] = hh;
-        lo[lane * 8 + j] = f2h((float)((w - (double)h2f(hh)) * H16_LO_SCALE));
+    for (int ks = 0; ks < KS_HID; ++ks) {
+      uint16_t* frag = (uint16_t*)(dst + ((size_t)to * kt + ks) * FRAG_BYTES);
+      for (int lane = 0; lane < 64; ++lane) {
+        const int r = lane & 31, h = lane >> 5;
+        for (int j = 0; j < 8; ++j) frag[lane * 8 + j] = f2h(wval(L, L.out_map[to * 32 + r], L.in_map[(ks * 2 + h) * 8 + j]) * P1_SKIP_SCALE);
       }
     }
+    uint16_t* his = (uint16_t*)(dst + ((size_t)to * kt + KS_HID) * FRAG_BYTES);
+    uint16_t* hi = (uint16_t*)(dst + ((size_t)to * kt + KS_HID + 1) * FRAG_BYTES);
+    pack_tile_f16x2(L, to, L.in_map.data() + KS_HID * 16, hi, (uint16_t*)(dst + ((size_t)to * kt + KS_HID + 2) * FRAG_BYTES));
+    for (int i = 0; i < 64 * 8; ++i) his[i] = f2h(h2f(hi[i]) * P1_SKIP_SCALE);
   }
 }
 
@@ -376,7 +399,8 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
   // Supported shapes (pnrf_layout.h, "free shape parameters"): width 256 and 8 samples per ray are fixed; free are the number of hidden layers
   // (mmnetdepth / netdepth), the sampler's ray points (N_point_ray_enc: input 6 P) and the refine net's neighbour views (num_neighbor: input 48 + 24 nb)
   static const char* SUPPORTED = "supported: hidden width 256, N_samples 8 (sampler 6*P -> D x 256 -> 27, any P >= 1; refine 48 + 24*nb -> D x 256 -> 35, nb = 1..8; "
-                                 "DoNeRFTRT 63 -> (netdepth - 1) x 256 -> [256 + 27] -> 4 with 3 <= netdepth <= 8; sampler / refine depth 2 <= D <= 32; the NeRF class: D = 8, skips = [4])";
+                                 "DoNeRFTRT 63 -> (netdepth - 1) x 256 -> [256 + 27] -> 4 with 3 <= netdepth <= 8; sampler / refine depth 2 <= D <= 32, skip connections (mmnetskips) behind "
+                                 "backbone layers 0 .. D - 2: such a layer has 256 + input width columns; the NeRF class: D = 8, skips = [4])";
   const int nhid = n_layers - 2;
   PNRF_REQUIRE(n_layers >= 3 && nhid <= MAX_NHID, PNRF_E_SHAPE, "pnrf_mlp_pack: net %d with %d Linear layers; %s", net, n_layers, SUPPORTED);
   const int in0 = in_dim[0];
@@ -395,14 +419,20 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
   }
   const int outN = net == PNRF_NET_SAMPLER ? S_OUT : net == PNRF_NET_REFINE ? R_OUT : N_OUT;
   const int last_in = net == PNRF_NET_NERF ? W_HID + N_INV : W_HID;
+  uint32_t skips = 0;                          // bit i: Linear i + 1 (hidden layer i of the kernels) reads cat([x, h]) — a skip behind backbone layer i
   for (int l = 0; l < n_layers; ++l) {
-    const int ei = l == 0 ? in0 : (l == n_layers - 1 ? last_in : W_HID);
+    int ei = l == 0 ? in0 : (l == n_layers - 1 ? last_in : W_HID);
     const int eo = l == n_layers - 1 ? outN : W_HID;
     PNRF_REQUIRE(W[l] && b[l], PNRF_E_ARG, "pnrf_mlp_pack: null weight/bias at layer %d", l);
+    if (net != PNRF_NET_NERF && l >= 1 && l < n_layers - 1 && in_dim[l] == W_HID + in0) { skips |= 1u << (l - 1); ei = W_HID + in0; }
     PNRF_REQUIRE(in_dim[l] == ei && out_dim[l] == eo, PNRF_E_SHAPE,
-                 "pnrf_mlp_pack: net %d layer %d is %dx%d where %dx%d is needed; %s", net, l, out_dim[l], in_dim[l], eo, ei, SUPPORTED);
+                 "pnrf_mlp_pack: net %d layer %d is %dx%d where %dx%d is needed (or %d input columns for a skip layer, cat([x, h]), behind backbone layers 0 .. D - 2); %s",
+                 net, l, out_dim[l], in_dim[l], eo, ei, W_HID + in0, SUPPORTED);
   }
-  const bool full_stream = net != PNRF_NET_SAMPLER || npts == S_NPTS;      // the sampler's unfolded stream (module-level forward, SAMPLER_F32_FULL): P = 48 only
+  PNRF_REQUIRE(!(net == PNRF_NET_REFINE && skips) || refine_skip_lds(n_layers - 2, 4, refine_nv(nbv)), PNRF_E_SHAPE,
+               "pnrf_mlp_pack: refine net with skip connections (mmnetskips), %d layers and %d neighbour views: its bias table and the parked net input do not fit the LDS beside "
+               "the weight ring (at most 31 layers with 7 or 8 views); %s", n_layers - 1, nbv, SUPPORTED);
+  const bool full_stream = net != PNRF_NET_SAMPLER || (npts == S_NPTS && !skips);      // the sampler's unfolded stream (module-level forward, SAMPLER_F32_FULL): P = 48, no skips
   const int nv = refine_nv(nbv);
 
   std::vector<Layer> Ls(n_layers);
@@ -413,6 +443,31 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     L.nk = prec == PREC_BF16 ? KS_HID : W_HID / 4;
     L.in_map = hidden_in(prec);
   }
+  // skip layers: W = [h-columns (256) | x-columns], the x-columns as the stream's first layer sees the input — the sampler's P ray points folded into one
+  // Pluecker 6-vector (fp64 sum, as wfold below), the refine net's as they are.  The hidden k-steps keep their maps; every stream appends its x k-steps
+  const int xw = net == PNRF_NET_SAMPLER ? 6 : in0;
+  std::vector<std::vector<float>> Wsk(n_layers);
+  for (int l = 1; l < n_layers - 1; ++l) {
+    if (!((skips >> (l - 1)) & 1u)) continue;
+    std::vector<float>& M = Wsk[l];
+    M.assign((size_t)W_HID * (W_HID + xw), 0.f);
+    for (int o = 0; o < W_HID; ++o) {
+      const float* row = W[l] + (size_t)o * (W_HID + in0);
+      float* dst = M.data() + (size_t)o * (W_HID + xw);
+      for (int c = 0; c < W_HID; ++c) dst[c] = row[in0 + c];
+      if (net == PNRF_NET_SAMPLER) {
+        for (int j = 0; j < 6; ++j) {
+          double acc = 0.0;
+          for (int pnt = 0; pnt < npts; ++pnt) acc += (double)row[6 * pnt + j];
+          dst[W_HID + j] = (float)acc;
+        }
+      } else {
+        for (int c = 0; c < in0; ++c) dst[W_HID + c] = row[c];
+      }
+    }
+    Ls[l].W = M.data(); Ls[l].in_dim = W_HID + xw; Ls[l].x_from = W_HID; Ls[l].slot_align = NSLOTS;
+  }
+  auto is_skip = [&](int l) { return l >= 1 && l < n_layers - 1 && ((skips >> (l - 1)) & 1u) != 0; };
   if (net == PNRF_NET_REFINE) scale_for_elu(Ls);          // every refine kernel computes its ELU on the log2(e) scale
   std::vector<int> in0_map, inx_map, out_map;
   Layer& F = Ls[0];
@@ -426,6 +481,15 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     const int ks0 = 3 * nv + 3;
     F.nk = ks0; F.in_map.assign(ks0 * 16, -1);
     for (int ks = 0; ks < ks0; ++ks) for (int h = 0; h < 2; ++h) for (int j = 0; j < 8; ++j) F.in_map[(ks * 2 + h) * 8 + j] = refine_in0_nv(nv, nbv, ks, h, j);
+    for (int l = 1; l < n_layers - 1; ++l)
+      if (is_skip(l)) {                          // per tile: the 16 hidden k-steps, then layer 0's k-steps on the x-columns
+        Layer& L = Ls[l];
+        L.nk = KS_HID + ks0; L.in_map.resize((size_t)L.nk * 16);
+        for (int ks = 0; ks < ks0; ++ks) for (int h = 0; h < 2; ++h) for (int j = 0; j < 8; ++j) {
+          const int v = refine_in0_nv(nv, nbv, ks, h, j);
+          L.in_map[((KS_HID + ks) * 2 + h) * 8 + j] = v >= 0 ? W_HID + v : -1;
+        }
+      }
     Z.nt = R_NT_LAST; Z.out_map.assign(64, -1);
     for (int h = 0; h < 2; ++h) for (int g = 0; g < 16; ++g) {
       Z.out_map[acc_row(g, h)] = refine_out0(g, h);
@@ -456,8 +520,8 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
   size_t slots = 0;
   for (auto& L : Ls) slots += layer_slots(L, prec);
   slots += (NSLOTS - slots % NSLOTS) % NSLOTS;
-  const uint32_t expect = net == PNRF_NET_SAMPLER ? s_nslots(nhid) : net == PNRF_NET_REFINE ? refine_slots(nhid, nv) : n_nslots(nhid);
-  PNRF_REQUIRE(slots == expect, PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (%zu slots, kernels expect %u)", slots, expect);
+  const uint32_t expect = net == PNRF_NET_SAMPLER ? s_nslots(nhid) : net == PNRF_NET_REFINE ? refine_slots(nhid, nv, skips) : n_nslots(nhid);
+  PNRF_REQUIRE(!full_stream || slots == expect, PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (%zu slots, kernels expect %u)", slots, expect);
   if (!full_stream) slots = 0;                   // no unfolded stream for this sampler
 
   std::vector<char> blob(slots * SLOT_BYTES, 0);
@@ -487,7 +551,7 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
   // the full first layer for rows from memory, and for the projecting head the first layer with the eight Pluecker 6-vectors folded into one (fp64 sum)
   std::vector<char> blob_r16, blob_r16f;
   std::vector<float> bias_r16, wfold_r;
-  if (net == PNRF_NET_REFINE) {
+  if (net == PNRF_NET_REFINE && !skips) {          // (PNRF_VARIANT_REFINE_16X16 does not take skip nets)
     const int nv4 = refine16_nv(nbv), fin = 6 + 24 * nbv;
     wfold_r.assign((size_t)W_HID * fin, 0.f);
     for (int o = 0; o < W_HID; ++o) {
@@ -547,9 +611,15 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     Layer& G = Lf[0];
     G.W = wfold.data(); G.in_dim = 6; G.nk = 4 * SF_KS4_0; G.in_map.assign(G.nk * 4, -1);
     for (int kk = 0; kk < 2; ++kk) for (int q = 0; q < 4; ++q) G.in_map[kk * 4 + q] = (4 * kk + q < 6) ? 4 * kk + q : -1;
+    for (int l = 1; l < n_layers - 1; ++l)
+      if (is_skip(l)) {                          // per tile: the 16 hidden fragments, then the folded input's one
+        Layer& L = Lf[l];
+        L.nk += 4 * SF_KS4_0; L.in_map.resize((size_t)L.nk * 4, -1);
+        for (int kk = 0; kk < 2; ++kk) for (int q = 0; q < 4; ++q) L.in_map[(W_HID / 4 + kk) * 4 + q] = (4 * kk + q < 6) ? W_HID + 4 * kk + q : -1;
+      }
     for (auto& L : Lf) slots_fold += layer_slots(L, prec);
     slots_fold += (NSLOTS - slots_fold % NSLOTS) % NSLOTS;
-    PNRF_REQUIRE(slots_fold == (size_t)sf_nslots(nhid), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (folded stream %zu slots, expected %d)", slots_fold, sf_nslots(nhid));
+    PNRF_REQUIRE(slots_fold == (size_t)sf_nslots(nhid, skips), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (folded stream %zu slots, expected %d)", slots_fold, sf_nslots(nhid, skips));
     blob_fold.assign(slots_fold * SLOT_BYTES, 0);
     size_t sf = 0;
     for (auto& L : Lf) { pack_layer(L, prec, blob_fold.data() + sf * SLOT_BYTES); sf += layer_slots(L, prec); }
@@ -568,10 +638,16 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     Layer& G = Lh[0];
     G.W = wfold.data(); G.in_dim = 6; G.nk = 1; G.in_map.assign(32, -1);
     for (int j = 0; j < 6; ++j) G.in_map[j] = j;               // group 0 holds the 6 Pluecker features, the rest is padding
-    auto hs = [&](const Layer& L) { return ((size_t)(L.nt / 2) * L.nk * 4 + SLOT_FRAGS - 1) / SLOT_FRAGS; };
+    for (int l = 1; l < n_layers - 1; ++l)
+      if (is_skip(l)) {                                        // a ninth k-step: the folded input, as layer 0's
+        Layer& L = Lh[l];
+        L.nk = SH_KS_H + 1; L.in_map.resize((size_t)L.nk * 32, -1);
+        for (int j = 0; j < 6; ++j) L.in_map[SH_KS_H * 32 + j] = W_HID + j;
+      }
+    auto hs = [&](const Layer& L) { return align_slots(L, ((size_t)(L.nt / 2) * L.nk * 4 + SLOT_FRAGS - 1) / SLOT_FRAGS); };
     for (auto& L : Lh) slots_h16 += hs(L);
     slots_h16 += (NSLOTS - slots_h16 % NSLOTS) % NSLOTS;
-    PNRF_REQUIRE(slots_h16 == (size_t)sh_nslots(nhid), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (f16x2 stream %zu slots, expected %d)", slots_h16, sh_nslots(nhid));
+    PNRF_REQUIRE(slots_h16 == (size_t)sh_nslots(nhid, skips), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (f16x2 stream %zu slots, expected %d)", slots_h16, sh_nslots(nhid, skips));
     blob_h16.assign(slots_h16 * SLOT_BYTES, 0);
     size_t sh = 0;
     for (auto& L : Lh) { pack_layer_h16x2(L, blob_h16.data() + sh * SLOT_BYTES); sh += hs(L); }
@@ -593,24 +669,32 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     Layer& Y = Lp[n_layers - 1];
     Y.nt = 1; Y.out_map.assign(32, -1);
     for (int hh = 0; hh < 2; ++hh) for (int g = 0; g < 16; ++g) Y.out_map[acc_row(g, hh)] = sampler_p1_out(g, hh);
-    blob_p1.assign((size_t)p1_nslots(nhid) * SLOT_BYTES, 0);
+    for (int l = 1; l < n_layers - 1; ++l)
+      if (is_skip(l)) {                                            // in_map = [16 hidden k-steps | the folded input's k-step]; fragments: pack_layer_f16_skip
+        Layer& L = Lp[l];
+        L.in_map.resize((size_t)(KS_HID + 1) * 16, -1);
+        for (int j = 0; j < 6; ++j) L.in_map[KS_HID * 16 + j] = W_HID + j;
+      }
+    blob_p1.assign((size_t)p1_nslots(nhid, skips) * SLOT_BYTES, 0);
     bias_p1.assign(p1_nbias(nhid), 0.f);
     size_t sp = 0, bp = 0;
     for (int l = 0; l < n_layers; ++l) {
       const Layer& L = Lp[l];
       if (l == 0) pack_layer0_f16x2(L, blob_p1.data());
+      else if (is_skip(l)) pack_layer_f16_skip(L, blob_p1.data() + sp * SLOT_BYTES);
       else pack_layer_f16(L, blob_p1.data() + sp * SLOT_BYTES);
       pack_bias(L, PREC_BF16, bias_p1.data() + bp);
-      sp += l == 0 ? P1_SLOTS_L0 : layer_slots(L, PREC_BF16);
+      if (is_skip(l)) for (int i = 0; i < L.nt * 32; ++i) bias_p1[bp + i] *= P1_SKIP_SCALE;      // the skip layer's accumulators run at scale 2^11
+      sp += l == 0 ? P1_SLOTS_L0 : is_skip(l) ? P1_SLOTS_SKIP : layer_slots(L, PREC_BF16);
       bp += (size_t)L.nt * 32;
     }
-    PNRF_REQUIRE(sp == (size_t)p1_slots_used(nhid) && bp == (size_t)p1_nbias(nhid), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (pass-1 stream %zu slots, %zu bias floats)", sp, bp);
+    PNRF_REQUIRE(sp == (size_t)p1_slots_used(nhid, skips) && bp == (size_t)p1_nbias(nhid), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (pass-1 stream %zu slots, %zu bias floats)", sp, bp);
     p1c.assign(p1_nconst(nhid), 0.f);             // [0] output-layer constant, [1 + l] C of hidden layer l (sampler_p1_kernel)
-    for (int l = 1; l <= nhid; ++l) {                             // C_l = max over input features j of the column norm sum_i W_l[i,j]^2
-      double cmax = 0.0;
+    for (int l = 1; l <= nhid; ++l) {                             // C_l = max over input features j of the column norm sum_i W_l[i,j]^2 — of a skip layer over
+      double cmax = 0.0;                                          // its h-columns only: the x-part is formed split-accurate like layer 0
       for (int j = 0; j < W_HID; ++j) {
         double cn = 0.0;
-        for (int i = 0; i < W_HID; ++i) { const double w = (double)W[l][(size_t)i * W_HID + j]; cn += w * w; }
+        for (int i = 0; i < W_HID; ++i) { const double w = (double)Ls[l].W[(size_t)i * Ls[l].in_dim + j]; cn += w * w; }
         cmax = cn > cmax ? cn : cmax;
       }
       p1c[l] = (float)(cmax * (1.0 + 1e-6));
@@ -664,7 +748,7 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
   pnrf_mlp* h = new pnrf_mlp();
   memset(h, 0, sizeof(*h));
   h->net = net; h->prec = prec; h->in_dim = in0; h->in_dim_x = net == PNRF_NET_NERF ? N_INV : 0; h->out_dim = outN;
-  h->nhid = nhid; h->nb = nbv; h->npts = npts;
+  h->nhid = nhid; h->nb = nbv; h->npts = npts; h->skips = skips;
   h->nslots = (uint32_t)slots; h->nbias = (int)nbias;
   h->n_in0 = (int)in0_map.size(); h->n_inx = (int)inx_map.size(); h->n_out = (int)out_map.size();
   hipError_t e = hipGetDevice(&h->device);
@@ -698,7 +782,7 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     if (e == hipSuccess) e = hipMemcpy(h->d_blob_f16, blob_f16.data(), blob_f16.size(), hipMemcpyHostToDevice);
   }
   if (e == hipSuccess && net == PNRF_NET_SAMPLER) {
-    h->nslots_p1 = p1_nslots(nhid); h->nbias_p1 = p1_nbias(nhid); h->n_p1c = p1_nconst(nhid);
+    h->nslots_p1 = p1_nslots(nhid, skips); h->nbias_p1 = p1_nbias(nhid); h->n_p1c = p1_nconst(nhid);
     e = hipMalloc(&h->d_blob_p1, blob_p1.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_blob_p1, blob_p1.data(), blob_p1.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_bias_p1, bias_p1.size() * sizeof(float));
@@ -713,7 +797,7 @@ extern "C" int pnrf_mlp_pack(int net, const float* const* W, const float* const*
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_bias_b16, bias_b16.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_bias_b16, bias_b16.data(), bias_b16.size() * sizeof(float), hipMemcpyHostToDevice);
   }
-  if (e == hipSuccess && net == PNRF_NET_REFINE) {
+  if (e == hipSuccess && net == PNRF_NET_REFINE && !skips) {
     h->nslots_b16 = (uint32_t)(blob_r16.size() / SLOT_BYTES); h->nbias_b16 = (int)bias_r16.size();
     e = hipMalloc(&h->d_blob_b16, blob_r16.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_blob_b16, blob_r16.data(), blob_r16.size(), hipMemcpyHostToDevice);
@@ -775,6 +859,7 @@ struct EngineHeader {
   int32_t net, prec, in_dim, in_dim_x, out_dim;
   uint32_t nslots, nslots_fold, nslots_h16, nslots_b16;
   int32_t nbias_b16, nbias, n_in0, n_inx, n_out, n_tvals;
+  uint32_t skips;                     // format 6: skip mask of a sampler / refine net (these four bytes were alignment padding, zero, in older formats)
   uint64_t payload_bytes, checksum;   // FNV-1a 64 of the payload
   uint32_t nslots_p1;                 // format 2: pass-1 stream of the two-pass sampler, its bias table and error-model constants
   int32_t nbias_p1, n_p1c;
@@ -782,7 +867,7 @@ struct EngineHeader {
   uint16_t nhid, nb, npts;            // format 4: the net's free shape parameters (hidden layers behind layer 0, neighbour views, ray points)
   uint8_t reserved[2];
 };
-static constexpr uint32_t ENGINE_FORMAT = 5;      // 5: refine handles carry the stream of the 16x16x32 engine (nslots_b16 / nbias_b16)
+static constexpr uint32_t ENGINE_FORMAT = 6;      // 6: sampler / refine handles carry their skip mask (mmnetskips); 5: refine handles carry the 16x16x32 stream
 static constexpr int ENGINE_SECTIONS = 14;
 static_assert(sizeof(EngineHeader) == 128, "engine header is 128 bytes");
 static const char ENGINE_MAGIC[8] = {'P', 'N', 'R', 'F', 'E', 'N', 'G', 0};
@@ -810,21 +895,21 @@ static int sections(pnrf_mlp* h, int n_tvals, Section* s) {
 }
 
 // what pnrf_mlp_pack produces for a net kind (the counts the kernels rely on)
-static void expected_counts(int net, int nhid, int nb, int npts, EngineHeader* w) {
+static void expected_counts(int net, int nhid, int nb, int npts, uint32_t skips, EngineHeader* w) {
   memset(w, 0, sizeof(*w));
-  w->nhid = (uint16_t)nhid; w->nb = (uint16_t)nb; w->npts = (uint16_t)npts;
+  w->nhid = (uint16_t)nhid; w->nb = (uint16_t)nb; w->npts = (uint16_t)npts; w->skips = skips;
   switch (net) {
     case PNRF_NET_SAMPLER: {
-      const bool full = npts == S_NPTS;
-      w->prec = PREC_F32; w->in_dim = 6 * npts; w->out_dim = S_OUT; w->nslots = full ? s_nslots(nhid) : 0; w->nslots_fold = sf_nslots(nhid); w->nslots_h16 = sh_nslots(nhid);
+      const bool full = npts == S_NPTS && !skips;
+      w->prec = PREC_F32; w->in_dim = 6 * npts; w->out_dim = S_OUT; w->nslots = full ? s_nslots(nhid) : 0; w->nslots_fold = sf_nslots(nhid, skips); w->nslots_h16 = sh_nslots(nhid, skips);
       w->nbias = s_nbias(nhid); w->n_in0 = S_KS0 * 4; w->n_out = 16 * S_NT_LAST; w->n_tvals = full ? S_NPTS : 0;
-      w->nslots_p1 = p1_nslots(nhid); w->nbias_p1 = p1_nbias(nhid); w->n_p1c = p1_nconst(nhid);
+      w->nslots_p1 = p1_nslots(nhid, skips); w->nbias_p1 = p1_nbias(nhid); w->n_p1c = p1_nconst(nhid);
       break;
     }
     case PNRF_NET_REFINE:
-      w->prec = PREC_BF16; w->in_dim = 48 + 24 * nb; w->out_dim = R_OUT; w->nslots = refine_slots(nhid, refine_nv(nb)); w->nbias = r_nbias(nhid);
+      w->prec = PREC_BF16; w->in_dim = 48 + 24 * nb; w->out_dim = R_OUT; w->nslots = refine_slots(nhid, refine_nv(nb), skips); w->nbias = r_nbias(nhid);
       w->n_in0 = (3 * refine_nv(nb) + 3) * 16; w->n_out = R_NT_LAST * 32;
-      w->nslots_b16 = refine16_slots(nhid, refine16_nv(nb), false); w->nslots_fold = refine16_slots(nhid, refine16_nv(nb), true); w->nbias_b16 = r16_nbias(nhid);
+      if (!skips) { w->nslots_b16 = refine16_slots(nhid, refine16_nv(nb), false); w->nslots_fold = refine16_slots(nhid, refine16_nv(nb), true); w->nbias_b16 = r16_nbias(nhid); }
       w->nslots_f16 = w->nslots;
       break;
     case PNRF_NET_NERF:
@@ -882,7 +967,7 @@ extern "C" int pnrf_mlp_serialize(const pnrf_mlp_t* hc, void* buf, int64_t capac
   hd.nslots = h->nslots; hd.nslots_fold = h->nslots_fold; hd.nslots_h16 = h->nslots_h16; hd.nslots_b16 = h->nslots_b16;
   hd.nbias_b16 = h->nbias_b16; hd.nbias = h->nbias; hd.n_in0 = h->n_in0; hd.n_inx = h->n_inx; hd.n_out = h->n_out; hd.n_tvals = n_tvals;
   hd.nslots_p1 = h->nslots_p1; hd.nbias_p1 = h->nbias_p1; hd.n_p1c = h->n_p1c; hd.nslots_f16 = h->nslots_f16;
-  hd.nhid = (uint16_t)h->nhid; hd.nb = (uint16_t)h->nb; hd.npts = (uint16_t)h->npts;
+  hd.nhid = (uint16_t)h->nhid; hd.nb = (uint16_t)h->nb; hd.npts = (uint16_t)h->npts; hd.skips = h->skips;
   hd.payload_bytes = payload;
   hd.checksum = fnv1a((const uint8_t*)buf + sizeof(EngineHeader), payload);
   memcpy(buf, &hd, sizeof(hd));
@@ -914,8 +999,10 @@ extern "C" int pnrf_mlp_deserialize(const void* buf, int64_t size, pnrf_mlp_t** 
                              (hd.net == PNRF_NET_SAMPLER ? (hd.npts >= 1 && hd.npts < 4096) : hd.npts == 0));
     PNRF_REQUIRE(shape_ok, PNRF_E_ARG, "pnrf_mlp_deserialize: shape parameters (hidden layers %u, views %u, ray points %u) outside what net kind %d supports",
                  hd.nhid, hd.nb, hd.npts, hd.net);
+    PNRF_REQUIRE(hd.skips == 0 || ((hd.net == PNRF_NET_SAMPLER || hd.net == PNRF_NET_REFINE) && skip_mask_ok(hd.skips, hd.nhid)), PNRF_E_ARG,
+                 "pnrf_mlp_deserialize: skip mask %08x outside what net kind %d with %u hidden layers supports", hd.skips, hd.net, hd.nhid);
     EngineHeader want;
-    expected_counts(hd.net, hd.nhid, hd.nb, hd.npts, &want);
+    expected_counts(hd.net, hd.nhid, hd.nb, hd.npts, hd.skips, &want);
     PNRF_REQUIRE(hd.prec == want.prec && hd.in_dim == want.in_dim && hd.in_dim_x == want.in_dim_x && hd.out_dim == want.out_dim &&
                      hd.nslots == want.nslots && hd.nslots_fold == want.nslots_fold && hd.nslots_h16 == want.nslots_h16 &&
                      hd.nslots_b16 == want.nslots_b16 && hd.nbias_b16 == want.nbias_b16 && hd.nbias == want.nbias && hd.n_in0 == want.n_in0 &&
@@ -929,7 +1016,7 @@ extern "C" int pnrf_mlp_deserialize(const void* buf, int64_t size, pnrf_mlp_t** 
   h->nslots = hd.nslots; h->nslots_fold = hd.nslots_fold; h->nslots_h16 = hd.nslots_h16; h->nslots_b16 = hd.nslots_b16;
   h->nbias_b16 = hd.nbias_b16; h->nbias = hd.nbias; h->n_in0 = hd.n_in0; h->n_inx = hd.n_inx; h->n_out = hd.n_out;
   h->nslots_p1 = hd.nslots_p1; h->nbias_p1 = hd.nbias_p1; h->n_p1c = hd.n_p1c; h->nslots_f16 = hd.nslots_f16;
-  h->nhid = hd.nhid; h->nb = hd.nb; h->npts = hd.npts;
+  h->nhid = hd.nhid; h->nb = hd.nb; h->npts = hd.npts; h->skips = hd.skips;
   Section sec[ENGINE_SECTIONS];
   const int ns = sections(h, hd.n_tvals, sec);
   size_t payload = 0;
@@ -971,6 +1058,9 @@ extern "C" int pnrf_mlp_set_variant(pnrf_mlp_t* h, int variant) {
                   (!sampler && variant == PNRF_VARIANT_BF16) || (h->net == PNRF_NET_REFINE && variant == PNRF_VARIANT_REFINE_16X16) || ((h->net == PNRF_NET_NERF || h->net == PNRF_NET_NERFCLS) && variant == PNRF_VARIANT_F16) ||
                   ((h->net == PNRF_NET_NERF || h->net == PNRF_NET_NERFCLS) && variant == PNRF_VARIANT_NERF_4X64);
   PNRF_REQUIRE(ok, PNRF_E_ARG, "pnrf_mlp_set_variant: variant %d does not exist for net kind %d", variant, h->net);
+  const bool no_skips = (h->net == PNRF_NET_REFINE && (variant == PNRF_VARIANT_REFINE_16X16 || variant == PNRF_VARIANT_BF16)) || (sampler && variant == PNRF_VARIANT_SAMPLER_F32_FULL);
+  PNRF_REQUIRE(!(h->skips && no_skips), PNRF_E_SHAPE, "pnrf_mlp_set_variant: variant %d is not built for nets with skip connections (mmnetskips; this net's mask: %08x); "
+               "the default kernels and the sampler's SAMPLER_SPLIT / SAMPLER_F32 variants take them", variant, h->skips);
   h->variant = variant;
   return 0;
 }
@@ -979,7 +1069,16 @@ extern "C" int pnrf_mlp_set_shape(pnrf_mlp_t* h, int shape) {
   PNRF_REQUIRE(h, PNRF_E_ARG, "pnrf_mlp_set_shape: null handle");
   PNRF_REQUIRE(shape == PNRF_SHAPE_AUTO || shape == PNRF_SHAPE_WIDE || shape == PNRF_SHAPE_NARROW, PNRF_E_ARG,
                "pnrf_mlp_set_shape: PNRF_SHAPE_AUTO (0), _WIDE (8) or _NARROW (4), got %d", shape);
+  PNRF_REQUIRE(!(shape == PNRF_SHAPE_WIDE && h->net == PNRF_NET_REFINE && h->skips && !(refine_nv(h->nb) <= 2 && refine_skip_lds(h->nhid, 8, refine_nv(h->nb)))), PNRF_E_SHAPE,
+               "pnrf_mlp_set_shape: PNRF_SHAPE_WIDE of the refine stage is not built for this net with skip connections (mmnetskips; %d neighbour views, %d hidden layers): its "
+               "parked net input fits the LDS of an 8-wave workgroup up to num_neighbor 4 (at 3 or 4 views: up to 18 hidden layers).  PNRF_SHAPE_AUTO launches it NARROW (same rows)", h->nb, h->nhid);
   h->shape = shape;
+  return 0;
+}
+
+extern "C" int pnrf_mlp_skips(const pnrf_mlp_t* h, uint32_t* mask) {
+  PNRF_REQUIRE(h && mask, PNRF_E_ARG, "pnrf_mlp_skips: null argument");
+  *mask = h->skips;
   return 0;
 }
 

@@ -63,6 +63,7 @@ class PackedMLP:
         self.net = net
         self.in_dim = ws[0].shape[1]
         self.out_dim = 4 if net == NET_NERFCLS else ws[-1].shape[0]      # NeRF class: [rgb(3), alpha]
+        self.skips = self._read_skips()
         self.variant = 'default'
         if variant not in (None, 'default'):
             self.set_variant(variant)
@@ -74,6 +75,12 @@ class PackedMLP:
         check(_lib.load().pnrf_mlp_set_variant(self.handle, _lib.VARIANTS[variant]), 'pnrf_mlp_set_variant')
         self.variant = variant
         return self
+
+    def _read_skips(self):
+        """Backbone layers of a sampler / refine stack behind which the net input is concatenated back (``--mmnetskips``), from the handle's mask."""
+        mask = C.c_uint32()
+        check(_lib.load().pnrf_mlp_skips(self.handle, C.byref(mask)), 'pnrf_mlp_skips')
+        return [i for i in range(32) if (mask.value >> i) & 1]
 
     SHAPES = {'auto': 0, 'narrow': 4, 'wide': 8}
 
@@ -115,6 +122,7 @@ class PackedMLP:
         net, ind, indx, outd = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         check(lib.pnrf_mlp_kind(h, C.byref(net), C.byref(ind), C.byref(indx), C.byref(outd)), 'pnrf_mlp_kind')
         self.net, self.in_dim, self.out_dim = net.value, ind.value, outd.value
+        self.skips = self._read_skips()
         self.variant = 'default'
         if expect_net is not None and self.net != expect_net:
             raise PnrfError(f'engine holds net kind {self.net}, expected {expect_net}')

@@ -125,6 +125,9 @@ def train(argv=None, device='cuda'):
         raise PnrfError('--no_ndc / --lindisp: the HIP path is built for forward-facing scenes in NDC with samples linear in depth (the LLFF configs)')
     if args.N_samples != 8 or args.num_neighbor != 4 or args.N_point_ray_enc != 48 or args.mmnetdepth != 6:
         raise PnrfError('the HIP trainer is built for N_samples=8, num_neighbor=4, N_point_ray_enc=48, mmnetdepth=6 (fern_epi.txt)')
+    if any(0 <= int(s) <= args.mmnetdepth - 2 for s in (getattr(args, 'mmnetskips', None) or [])):
+        raise PnrfError(f'--mmnetskips {list(args.mmnetskips)} names a layer inside the sampler / refine stacks: the HIP trainer builds them without skip '
+                        'connections (set mmnetskips beyond the depth, as the Fern configs do); the inference path takes skip nets')
     replica, world, dev = dist_setup(device)
     if args.N_rand % world:
         raise ValueError(f'N_rand = {args.N_rand} is not divisible by the {world} replicas')

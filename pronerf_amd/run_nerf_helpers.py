@@ -142,7 +142,12 @@ class _PackedNet(nn.Module):
         if dev.type != 'cuda':
             raise PnrfError(f'{type(self).__name__}: move the module to the GPU before load_engine (pronerf_amd has no CPU path)')
         with torch.cuda.device(dev):
-            self._packed = ops.PackedMLP.load(path, expect_net=self._NET)
+            packed = ops.PackedMLP.load(path, expect_net=self._NET)
+        # a sampler / refine engine carries its skip set (--mmnetskips): it must be the one this module was built with
+        mine = sorted({int(s) for s in self.skips if 0 <= int(s) <= self.D - 2}) if isinstance(self, MinMaxRay_Net) else None
+        if mine is not None and packed.skips != mine:
+            raise PnrfError(f'{type(self).__name__}: the engine at {path} holds a net with skip connections {packed.skips}, this module was built with {mine} (--mmnetskips)')
+        self._packed = packed
         self._pack_key = self._param_key()
         self.engine_path = path
 
@@ -153,7 +158,8 @@ class _PackedNet(nn.Module):
 
 class MinMaxRay_Net(_PackedNet):
     """Sampler backbone, raw outputs (helpers:1440-1471).  Shapes the kernels take (round 6: the reference's free ``--mmnetdepth``,
-    ``--N_point_ray_enc``, ``--num_neighbor``, run_S_eS_eN_alter_trt.py:62-82, 427-457): W = 256, no skip inside the stack, any depth D >= 2,
+    ``--N_point_ray_enc``, ``--num_neighbor``, ``--mmnetskips``, run_S_eS_eN_alter_trt.py:62-82, 427-457): W = 256, any depth D >= 2, skip connections behind
+    backbone layers 0 .. D - 2 (an entry beyond the depth, as the Fern configs' 10000, names no layer; D - 1 would feed ``fc_output``, which the reference itself cannot run),
     sampler 6 * N_point_ray_enc -> 27 (any number of ray points), refine 48 + 24 * num_neighbor -> 35 (1 .. 8 neighbour views); N_samples = 8.
     The Fern configs are D = 6, 288 -> 27 and 144 -> 35."""
 
@@ -167,12 +173,12 @@ class MinMaxRay_Net(_PackedNet):
             self._NET = ops.NET_SAMPLER
         elif output_ch == 35 and input_ch >= 72 and (input_ch - 48) % 24 == 0 and (input_ch - 48) // 24 <= 8:
             self._NET = ops.NET_REFINE
-        self._supported = (2 <= D <= 32 and W == 256 and not any(0 <= s < D - 1 for s in skips) and self._NET is not None)
+        self._supported = (2 <= D <= 32 and W == 256 and D - 1 not in skips and self._NET is not None)
 
     def _linears(self):
         if not self._supported:
             raise PnrfError(f'{type(self).__name__}(D={self.D}, W={self.W}, input_ch={self.input_ch}, skips={self.skips}): '
-                            'the HIP kernels take W=256, no skips inside the stack, 2 <= D <= 32, and 6*N_point_ray_enc -> 27 (sampler) or '
+                            'the HIP kernels take W=256, skips behind backbone layers 0 .. D-2, 2 <= D <= 32, and 6*N_point_ray_enc -> 27 (sampler) or '
                             '48 + 24*num_neighbor -> 35 with 1 <= num_neighbor <= 8 (refine); N_samples = 8')
         return list(self.fc_backbone) + [self.fc_output]
 

@@ -65,9 +65,12 @@ def _mlp(rs, dims, kind):
 
 
 def make_weights(seed: int = 0, kind: str = 'trained', n_pts: int = N_POINT_RAY_ENC, mmnetdepth: int = MMNETDEPTH, num_neighbor: int = NUM_NEIGHBOR,
-                 netdepth: int = NETDEPTH):
+                 netdepth: int = NETDEPTH, mmnetskips=()):
     """Three weight sets as lists of numpy arrays (torch layout ``W[out,in]``).  n_pts / mmnetdepth / num_neighbor / netdepth: the reference's free
     shape arguments (``--N_point_ray_enc --mmnetdepth --num_neighbor --netdepth``, run_S_eS_eN_alter_trt.py:62-82, 427-457); defaults = fern_trt.txt.
+    mmnetskips: backbone layers of the sampler / refine stacks behind which the net input is concatenated back (``--mmnetskips``; entries beyond
+    mmnetdepth - 2 are ignored like the Fern configs' 10000): Linear i + 1 becomes ``[256, in_ch + 256]`` = [x-columns | h-columns].  The h-columns are the
+    draws of the net without skips and the x-columns come from a generator of their own, so every other array is bit-identical to ``mmnetskips=()``.
 
     kind:
       'default'  module default initialisation (sampler/refine: nn.Linear default;
@@ -120,6 +123,14 @@ def make_weights(seed: int = 0, kind: str = 'trained', n_pts: int = N_POINT_RAY_
         rW[-1] = rW[-1] * 0.35
         nW[-1] = nW[-1] * 0.5
         nb[-1] = nb[-1].copy(); nb[-1][3] += 1.0
+    skips = sorted({int(i) for i in mmnetskips if 0 <= int(i) <= mmnetdepth - 2})
+    if skips:
+        xs = np.random.RandomState(9000011 * (seed + 1) + {'default': 0, 'spread': 1, 'trained': 2}[kind])
+        for Ws, in_ch, gain in ((sW, sampler_dims[0], 4.0 if adversarial == 'x4' else 1.0), (rW, refine_dims[0], 1.0)):
+            for i in skips:
+                wb = (1.0 / np.sqrt(in_ch)) if kind != 'trained' else np.sqrt(6.0 / in_ch) * 0.5
+                Wx = _uniform(xs, (MMNETWIDTH, in_ch), wb) * np.float32(gain)
+                Ws[i + 1] = np.ascontiguousarray(np.concatenate([Wx, Ws[i + 1]], axis=1), dtype=np.float32)
     return {
         'sampler': {'W': sW, 'b': sb},
         'refine': {'W': rW, 'b': rb},
@@ -149,8 +160,9 @@ def make_nerfcls_weights(seed: int = 0, head_scale: float = 1.0):
     return out
 
 
-def state_dicts(weights):
-    """numpy weights -> the reference modules' ``state_dict`` key layout.
+def state_dicts(weights, mmnetskips=()):
+    """numpy weights -> the reference modules' ``state_dict`` key layout.  mmnetskips, if given, is checked against the stacks' shapes
+    (``make_weights(..., mmnetskips=...)``: Linear i + 1 of a skip i has in_ch + 256 columns).
 
     sampler/refine: ``fc_backbone.{i}.*``, ``fc_output.*`` (run_nerf_helpers.py:1484-1488);
     DoNeRFTRT: ``layers.{i}.*`` (run_nerf_helpers.py:1235-1239).
@@ -159,6 +171,10 @@ def state_dicts(weights):
     out = {}
     for name in ('sampler', 'refine'):
         W, b = weights[name]['W'], weights[name]['b']
+        have = [i - 1 for i in range(1, len(W) - 1) if W[i].shape[1] == W[0].shape[1] + W[i].shape[0]]
+        want = sorted({int(i) for i in mmnetskips if 0 <= int(i) <= len(W) - 3})
+        if mmnetskips and have != want:
+            raise ValueError(f'{name}: the weights carry skips {have}, mmnetskips asks for {want}')
         sd = {}
         for i in range(len(W) - 1):
             sd[f'fc_backbone.{i}.weight'] = torch.from_numpy(W[i].copy())

@@ -36,6 +36,11 @@ def load_lib(name):
         f = getattr(lib, fn, None)            # an older build under comparison may lack the newest entry points
         if f is not None:
             f.restype = res; f.argtypes = args
+    if getattr(lib, 'pnrf_mlp_skips', None) is None:      # a build from before skip connections holds no skip nets: report none (ops.PackedMLP asks every handle)
+        def no_skips(handle, mask):
+            mask._obj.value = 0
+            return 0
+        lib.pnrf_mlp_skips = no_skips
     return lib
 
 
