@@ -382,13 +382,18 @@ int pnrf_ctx_profile_end(pnrf_ctx_t* ctx, float* ms, int* frames);
 int pnrf_composite_bwd(const float* raw, const float* z, const float* rays_d, int d_stride, const float* add,
                        const float* mul, const float* noise, float clamp, int white_bkgd, const float* d_rgb,
                        float* d_raw, float* d_z, float* d_add, float* d_mul, int64_t n, int s, void* stream);
-/* Embedder.embed backward: d_x[n,3] from d_out[n, 3+6*n_freq] (run_nerf_helpers.py:666-671). */
+/* Embedder.embed backward: d_x[n,3] from d_out[n, 3+6*n_freq] (run_nerf_helpers.py:666-671).  n_freq 0..16; at x = 0 the result
+ * is exactly d_out[c] + sum_k 2^k d_out[sin_k] (tests/test_exact_heads_gpu.py pins it there, and forward and backward elsewhere
+ * within a per-element bound, past the grid cap included). */
 int pnrf_posenc_bwd(const float* x, const float* d_out, float* d_x, int64_t n, int n_freq, void* stream);
 /* Sampler head on the raw output y dev [n,27] of MinMaxRay_Net: depth = sigmoid(y[0:8]) (far-near)+near, stable ascending
  * sort, add / mul gathered by the sort indices, mm_rgb = sigmoid(y[24:27]) (NULL to skip)
- * (run_S_eS_eN_alter_base_refine2.py:557-568); the backward scatters through sort_idx. */
+ * (run_S_eS_eN_alter_base_refine2.py:557-568); the backward scatters through sort_idx.
+ * Forward: tied depths keep their index order; a NaN depth still gives a permutation of 0..7 in sort_idx, at an unspecified
+ * place, and stays in its ray. */
 int pnrf_sampler_head_fwd(const float* y, const float* rays, float* depth_sorted, int64_t* sort_idx, float* add_sorted,
                           float* mul_sorted, float* mm_rgb, int64_t n, void* stream);
+/* Backward: sort_idx as the forward wrote it (ties included); d_mm_rgb NULL gives exact zeros in d_y[:, 24:27]. */
 int pnrf_sampler_head_bwd(const float* y, const float* rays, const int64_t* sort_idx, const float* d_depth_sorted,
                           const float* d_add_sorted, const float* d_mul_sorted, const float* d_mm_rgb, float* d_y,
                           int64_t n, void* stream);
@@ -396,9 +401,12 @@ int pnrf_sampler_head_bwd(const float* y, const float* rays, const int64_t* sort
  * (NULL to skip); interval refinement, depth jitter (jitter dev [n,8] or NULL, jitter_dir +-1), query points
  * pts dev [n,8,3] = o + d z + 0.01 offsets; z_pre dev [n,8] = depths before the jitter (input of the backward)
  * (run_S_eS_eN_alter_base_refine2.py:635-668).  Backward: d_pts dev [n,8,3], d_z dev [n,8] or NULL, d_rgb0 dev [n,3] or
- * NULL -> d_y dev [n,35], d_depth_sorted dev [n,8]. */
+ * NULL -> d_y dev [n,35], d_depth_sorted dev [n,8].
+ * Forward: depth_sorted need not be sorted (the formulas are applied to whatever order it holds); a NaN stays in its ray. */
 int pnrf_refine_head_fwd(const float* y, const float* rays, const float* depth_sorted, const float* jitter,
                          int jitter_dir, float* z_pre, float* z, float* pts, float* rgb0, int64_t n, void* stream);
+/* Backward: depth_sorted need not be sorted either: |z_pre - neighbour| is differentiated by the sign it has (0 at a tie, as
+ * torch's abs); d_z NULL counts as zeros, d_rgb0 NULL gives exact zeros in d_y[:, 32:35]. */
 int pnrf_refine_head_bwd(const float* y, const float* rays, const float* depth_sorted, const float* z_pre,
                          const float* jitter, int jitter_dir, const float* d_pts, const float* d_z,
                          const float* d_rgb0, float* d_y, float* d_depth_sorted, int64_t n, void* stream);

@@ -17,6 +17,8 @@ The per-ray kernels between the MLPs — ``composite_kernel`` / ``composite_thre
       - ``Mag``: float64 values with a running magnitude (see ``BOUND_DOC``), for the per-element bound of the general regime.
   * ``exact_inputs`` / ``random_inputs``: the two regimes' input sets; ``reference``: the oracle's raw2outputs in float64 plus autograd.
   * ``MUTATIONS``: one slip each, applied by ``replay(..., mutation=...)``.
+
+The back ends also carry the operations of the head and positional-encoding kernels (scale, tanh, sin, cos, abs, sign): tests/exact_heads.py.
 """
 from __future__ import annotations
 
@@ -85,6 +87,13 @@ class F32:
     def max_nan(self, c, a): return np.where(np.isnan(a), a, np.maximum(np.float32(c), a))       # torch.max: NaN propagates
     def where(self, c, a, b): return np.where(c, a, b).astype(np.float32)
     def cond(self, a): return a
+    # ---- what tests/exact_heads.py adds (the heads' and the positional encoding's operations)
+    def scale(self, a, p): return np.float32(a) * np.float32(p)                                  # p a power of two: exact
+    def tanh(self, a): return np.tanh(np.float32(a))
+    def sin(self, a): return np.sin(np.float32(a))
+    def cos(self, a): return np.cos(np.float32(a))
+    def abs(self, a): return np.abs(a)
+    def sign(self, a): return np.sign(a).astype(np.float32)                                      # +1 / -1 / 0 (NaN passes)
 
 
 class V:
@@ -186,6 +195,31 @@ class Cert:
         assert not np.any(a.t), 'a branch depends on a tainted value'
         return a.v
 
+    # ---- what tests/exact_heads.py adds
+    def scale(self, a, p):
+        """a * p for a power of two p (one rounding, checked like any product)."""
+        return self._round('scale', a.v * float(p), a.t)
+
+    def tanh(self, a):
+        """tanhf: exactly +-1 from |a| >= 200 on and exactly 0 at 0; anything else taints."""
+        one, mone, zero = (a.v >= 200) & ~a.t, (a.v <= -200) & ~a.t, (a.v == 0) & ~a.t
+        bad = ~(one | mone | zero)
+        self._taint('tanh argument neither 0 nor |.| >= 200', bad)
+        return V(np.where(one, 1.0, np.where(mone, -1.0, np.where(zero, 0.0, np.tanh(a.v)))), bad)
+
+    def sin(self, a):
+        bad = ~((a.v == 0) & ~a.t)
+        self._taint('sin argument not 0', bad)
+        return V(np.where(bad, np.sin(a.v), 0.0), bad)
+
+    def cos(self, a):
+        bad = ~((a.v == 0) & ~a.t)
+        self._taint('cos argument not 0', bad)
+        return V(np.where(bad, np.cos(a.v), 1.0), bad)
+
+    def abs(self, a): return V(np.abs(a.v), a.t)
+    def sign(self, a): return V(np.sign(a.v), a.t)               # the sign of an exact value; a tainted one taints what it decides
+
 
 BOUND_DOC = """Per-element bound of the general regime:  |got - ref| <= 2 (S + 9) 2^-24 mag (1 + 2^-10) + (S + 9) 2^-126.
 
@@ -249,6 +283,14 @@ class Mag:
     def max_nan(self, c, a): return V(np.where(np.isnan(a.v), a.v, np.maximum(float(np.float32(c)), a.v)), a.t)
     def where(self, c, a, b): return V(np.where(c, a.v, b.v), np.where(c, a.t, b.t))
     def cond(self, a): return a.v
+    # ---- what tests/exact_heads.py adds.  tanh / sin / cos of an argument that carries no error (an input, or an input times 2^k):
+    # m = |result|; the function's own error counts as roundings in the bound's d (exact_heads.BOUND_DOC), as sigmoid's does above.
+    def scale(self, a, p): return V(a.v * float(p), a.t * abs(float(p)))
+    def tanh(self, a): return V(np.tanh(a.v), np.abs(np.tanh(a.v)))
+    def sin(self, a): return V(np.sin(a.v), np.abs(np.sin(a.v)))
+    def cos(self, a): return V(np.cos(a.v), np.abs(np.cos(a.v)))
+    def abs(self, a): return V(np.abs(a.v), a.t)
+    def sign(self, a): return V(np.sign(a.v), np.abs(np.sign(a.v)))    # decided alike in both precisions (the input sets see to that)
 
 
 def bound(S, mag):
