@@ -178,23 +178,27 @@ int pnrf_ndc_rays_fwd(const float* rays_o, const float* rays_d, int H, int W, fl
 /* inverse_warp_rod1_rt2_coords_trt: img dev [B,3,Hf,Wf]; depth dev [B,n]; ro1,rd1 dev [4,n] per
  * batch entry with batch stride ray_bstride floats (0 = shared by all B, the reference's
  * expand()); w2c dev [B,3,4]; out dev [B,3,n].
- * Bilinear, zero padding, align_corners=True (inverse_warp.py:584-619). */
+ * Bilinear, zero padding, align_corners=True (inverse_warp.py:584-619).
+ * Pinned bit for bit by tests/test_exact_project_gpu.py (fp32 replay: tests/exact_project.py). */
 int pnrf_warp_trt_fwd(const float* img, const float* depth, const float* ro1, const float* rd1,
                       int64_t ray_bstride, const float* w2c, float* out, int B, int Hf, int Wf,
                       int64_t n, void* stream);
 /* inverse_warp_rod1_rt2_coords (training variant): c2 = R^T w - R^T t, c2 /= |c2.z|+1e-8, c2.z = 1, c2.y = -c2.y,
  * p = K c2; samples whose normalised X or Y leaves [-1,1] give 0.  img dev [B,3,Hf,Wf]; depth dev [B,n]; ro1, rd1 dev
  * [3,n] per batch entry (batch stride ray_bstride floats, 0 = shared); c2w2 dev [B,3,4]; K dev [B,3,3]; out dev
- * [B,3,n]  (inverse_warp.py:515-581). */
+ * [B,3,n]  (inverse_warp.py:515-581).
+ * Pinned bit for bit by tests/test_exact_project_gpu.py, the mask's boundary xn, yn == +-1 (inside) included. */
 int pnrf_warp_train_fwd(const float* img, const float* depth, const float* ro1, const float* rd1,
                         int64_t ray_bstride, const float* c2w2, const float* K, float* out, int B, int Hf,
                         int Wf, int64_t n, void* stream);
 /* Neighbour images [nv,3,Hf,Wf] -> texel-interleaved [nv,Hf,Wf,4] used by the fused projection
- * (replaces the x8 image replication of run_S_eS_eN_alter_trt.py:296-298). */
+ * (replaces the x8 image replication of run_S_eS_eN_alter_trt.py:296-298).  Texels must be finite (pnrf_geom.h). */
 int pnrf_images_pack(const float* img_nchw, float* out_nhwc4, int nv, int Hf, int Wf, void* stream);
 /* Projection + sample Pluecker: refine_in[n, 48 + 24 nb] (nb = 4: [n,144]) = [pluecker(8 samples)(48), epi(24 nb)], nb = 1 .. 8, with
  * epi index (k*8+s)*3+c  (run_S_eS_eN_alter_trt.py:637-661).  rays,or_rays dev [n,11];
- * depth_sorted dev [n,8]; img4 dev [nb,Hf,Wf,4]; proj dev [nb,3,4]; eps = 1e-5 (stage 1: 1e-6). */
+ * depth_sorted dev [n,8]; img4 dev [nb,Hf,Wf,4]; proj dev [nb,3,4]; eps = 1e-5 (stage 1: 1e-6).
+ * Non-finite pixel coordinates (p.z == 0) give zeros in their own three columns.
+ * Pinned bit for bit by tests/test_exact_project_gpu.py for nb = 1 .. 8. */
 int pnrf_refine_input_fwd(const float* rays, const float* or_rays, const float* depth_sorted,
                           const float* img4, const float* proj, int nb, int Hf, int Wf, float eps,
                           float* refine_in, int64_t n, void* stream);
@@ -203,7 +207,8 @@ int pnrf_refine_input_fwd(const float* rays, const float* or_rays, const float* 
  * projection (pnrf_warp_train_fwd) and the valid-mask mean fill: valid = (sum_c rgb > 0), invalid (view, sample)
  * entries are replaced by the mean over the valid views of that sample.  K dev [3,3].  layout 0: epi index
  * (k*8+s)*3+c (stage 2); 1: s*12+k*3+c (stage 1).
- * (run_S_eS_eN_alter_base_refine2.py:570-634; run_S_eS_eN_alter_base.py:607-673) */
+ * (run_S_eS_eN_alter_base_refine2.py:570-634; run_S_eS_eN_alter_base.py:607-673)
+ * ref_nos outside 0 .. nv - 1 are clamped.  Pinned bit for bit, both layouts, by tests/test_exact_project_gpu.py. */
 int pnrf_refine_input_train_fwd(const float* rays, const float* or_rays, const float* depth_sorted,
                                 const float* img4, const float* poses, const float* K, const int64_t* ref_nos,
                                 int nv, int nb, int Hf, int Wf, float eps, int layout, float* refine_in,
@@ -274,7 +279,8 @@ int pnrf_refine_fwd(const pnrf_mlp_t* h, const float* refine_in, const float* ra
  * the colours and encodes the sample Pluecker values in the head of its batch, straight into the MFMA operand registers.
  * rays, or_rays dev [n,11]; depth_sorted dev [n,8]; img4 dev [nb,Hf,Wf,4] (pnrf_images_pack); proj dev [nb,3,4]; eps as pnrf_refine_input_fwd;
  * nb must be the handle's num_neighbor (1 .. 8; 4 in the Fern configs: a lane half then projects two views, ceil(nb / 2) in general).
- * This is the refine stage of pnrf_render_rays_fwd.  (run_S_eS_eN_alter_trt.py:637-681; inverse_warp.py:584-619) */
+ * This is the refine stage of pnrf_render_rays_fwd.  (run_S_eS_eN_alter_trt.py:637-681; inverse_warp.py:584-619)
+ * Pinned by tests/test_exact_project_gpu.py: on integer nets and colours it equals pnrf_refine_fwd on the reference's refine_in. */
 int pnrf_refine_project_fwd(const pnrf_mlp_t* h, const float* rays, const float* or_rays, const float* depth_sorted,
                             const float* img4, const float* proj, int nb, int Hf, int Wf, float eps, float* z,
                             float* pts, int64_t n, void* stream);

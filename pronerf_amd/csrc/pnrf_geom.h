@@ -43,8 +43,16 @@ __device__ __forceinline__ void bilinear_setup(float X, float Y, int Hf, int Wf,
 // metric depth 1 / (1 - dn - eps) -> world point w = o + e z -> pixel (X, Y) = (M w)_{0,1} / (M w)_2 with the 3x4 matrix M -> the four
 // bilinear taps as texel indices into a [Hf, Wf] float4 image and their weights.  A tap outside the image gets weight 0 and a clamped
 // (valid) index: t * 0 = 0 and x + 0 = x exactly, so fetching unconditionally gives the bits of the reference's zero padding without a
-// divergent branch per tap.
+// divergent branch per tap.  CONTRACT: the images hold finite texels — t * 0 is 0 for a finite t only; an inf or NaN texel at a clamped
+// index would reach the colours of samples that never see it in the reference.
 struct Taps { uint32_t i00, i01, i10, i11; float a00, a01, a10, a11; };      // texel indices (clamped into the image: never negative)
+// The four tap weights of bilinear_setup's cell: a tap that is not fetched (outside the image, or a sample outside the training mask)
+// gets weight 0 next to its texel 0 — non-finite coordinates make wx, wy NaN, and 0 * NaN is not 0.  One statement for every kernel.
+__device__ __forceinline__ void tap_weights(float wx0, float wx1, float wy0, float wy1, bool ok00, bool ok01, bool ok10, bool ok11,
+                                            float& a00, float& a01, float& a10, float& a11) {
+  a00 = ok00 ? ieee_mul(wx0, wy0) : 0.f; a01 = ok01 ? ieee_mul(wx1, wy0) : 0.f;
+  a10 = ok10 ? ieee_mul(wx0, wy1) : 0.f; a11 = ok11 ? ieee_mul(wx1, wy1) : 0.f;
+}
 __device__ __forceinline__ Taps project_taps(float o0, float o1, float o2, float e0, float e1, float e2, float dn, float eps, const float (&M)[12], int Hf, int Wf) {
   const float z3d = ieee_div(1.f, ieee_sub(ieee_sub(1.f, dn), eps));                                                   // trt.py:637
   const float w0 = ieee_add(o0, ieee_mul(e0, z3d)), w1 = ieee_add(o1, ieee_mul(e1, z3d)), w2 = ieee_add(o2, ieee_mul(e2, z3d));   // inverse_warp.py:600
@@ -59,8 +67,7 @@ __device__ __forceinline__ Taps project_taps(float o0, float o1, float o2, float
   const int xa = min(max(x0, 0), Wf - 1), xb = min(max(x0 + 1, 0), Wf - 1), ya = min(max(y0, 0), Hf - 1), yb = min(max(y0 + 1, 0), Hf - 1);
   Taps t;
   t.i00 = ya * Wf + xa; t.i01 = ya * Wf + xb; t.i10 = yb * Wf + xa; t.i11 = yb * Wf + xb;
-  t.a00 = (oky0 && okx0) ? ieee_mul(wx0, wy0) : 0.f; t.a01 = (oky0 && okx1) ? ieee_mul(wx1, wy0) : 0.f;
-  t.a10 = (oky1 && okx0) ? ieee_mul(wx0, wy1) : 0.f; t.a11 = (oky1 && okx1) ? ieee_mul(wx1, wy1) : 0.f;
+  tap_weights(wx0, wx1, wy0, wy1, oky0 && okx0, oky0 && okx1, oky1 && okx0, oky1 && okx1, t.a00, t.a01, t.a10, t.a11);
   return t;
 }
 // The same projection for the fused refine head, where the 96 colours of a ray go straight into bf16 MFMA operands (8 significant bits):

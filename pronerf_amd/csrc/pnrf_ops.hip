@@ -178,7 +178,8 @@ __global__ __launch_bounds__(256) void refine_input_kernel(const float* __restri
       const float4 t01 = (oky0 && okx1) ? im[(int64_t)y0 * Wf + x0 + 1] : zero;
       const float4 t10 = (oky1 && okx0) ? im[(int64_t)(y0 + 1) * Wf + x0] : zero;
       const float4 t11 = (oky1 && okx1) ? im[(int64_t)(y0 + 1) * Wf + x0 + 1] : zero;
-      const float a00 = ieee_mul(wx0, wy0), a01 = ieee_mul(wx1, wy0), a10 = ieee_mul(wx0, wy1), a11 = ieee_mul(wx1, wy1);
+      float a00, a01, a10, a11;
+      tap_weights(wx0, wx1, wy0, wy1, oky0 && okx0, oky0 && okx1, oky1 && okx0, oky1 && okx1, a00, a01, a10, a11);
       const int f = 48 + (k * 8 + s) * 3;                                                        // epi index (k*8+s)*3+c
       sT[(f + 0) * (RI_TILE + 1) + lane] = ieee_add(ieee_add(ieee_add(ieee_mul(t00.x, a00), ieee_mul(t01.x, a01)), ieee_mul(t10.x, a10)), ieee_mul(t11.x, a11));
       sT[(f + 1) * (RI_TILE + 1) + lane] = ieee_add(ieee_add(ieee_add(ieee_mul(t00.y, a00), ieee_mul(t01.y, a01)), ieee_mul(t10.y, a10)), ieee_mul(t11.y, a11));
@@ -302,7 +303,8 @@ __global__ void refine_input_train_kernel(const float* __restrict__ rays, const 
     const float4 t01 = (oky0 && okx1) ? im[(int64_t)y0 * Wf + x0 + 1] : zero;
     const float4 t10 = (oky1 && okx0) ? im[(int64_t)(y0 + 1) * Wf + x0] : zero;
     const float4 t11 = (oky1 && okx1) ? im[(int64_t)(y0 + 1) * Wf + x0 + 1] : zero;
-    const float a00 = ieee_mul(wx0, wy0), a01 = ieee_mul(wx1, wy0), a10 = ieee_mul(wx0, wy1), a11 = ieee_mul(wx1, wy1);
+    float a00, a01, a10, a11;               // (a NaN weight beside a zero texel would fill the mean of the sample's other views)
+    tap_weights(wx0, wx1, wy0, wy1, oky0 && okx0, oky0 && okx1, oky1 && okx0, oky1 && okx1, a00, a01, a10, a11);
     float v[3];
     v[0] = ieee_add(ieee_add(ieee_add(ieee_mul(t00.x, a00), ieee_mul(t01.x, a01)), ieee_mul(t10.x, a10)), ieee_mul(t11.x, a11));
     v[1] = ieee_add(ieee_add(ieee_add(ieee_mul(t00.y, a00), ieee_mul(t01.y, a01)), ieee_mul(t10.y, a10)), ieee_mul(t11.y, a11));

@@ -18,7 +18,8 @@ The per-ray kernels between the MLPs — ``composite_kernel`` / ``composite_thre
   * ``exact_inputs`` / ``random_inputs``: the two regimes' input sets; ``reference``: the oracle's raw2outputs in float64 plus autograd.
   * ``MUTATIONS``: one slip each, applied by ``replay(..., mutation=...)``.
 
-The back ends also carry the operations of the head and positional-encoding kernels (scale, tanh, sin, cos, abs, sign): tests/exact_heads.py.
+The back ends also carry the operations of the head and positional-encoding kernels (scale, tanh, sin, cos, abs, sign): tests/exact_heads.py,
+and those of the projection and texel-fetch kernels (floor, fma, comparisons, texel): tests/exact_project.py.
 """
 from __future__ import annotations
 
@@ -69,6 +70,20 @@ def f32(x):
     return np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
 
 
+def fma32(a, b, c):
+    """fl32(a b + c) with one rounding, on float32 arrays: the product of two fp32 values is exact in float64; the float64 sum is
+    corrected to round-to-odd with TwoSum's error term, so that the final rounding to fp32 sees the exact sum's sticky bit."""
+    a, b, c = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
+    with np.errstate(all='ignore'):
+        p = a * b
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
 class F32:
     """numpy float32: one IEEE rounding per operation (what the kernels' ieee_* helpers do)."""
     def inp(self, x): return np.asarray(x, np.float32)
@@ -94,6 +109,18 @@ class F32:
     def cos(self, a): return np.cos(np.float32(a))
     def abs(self, a): return np.abs(a)
     def sign(self, a): return np.sign(a).astype(np.float32)                                      # +1 / -1 / 0 (NaN passes)
+    # ---- what tests/exact_project.py adds (projection and texel fetch): floor, a fused multiply-add, comparisons, a constant absorbed
+    def val(self, a): return np.asarray(a)                                                       # the plain values (indices, branches)
+    def floor(self, a): return np.floor(np.float32(a))
+    def rint(self, a): return np.rint(np.float32(a))
+    def fma(self, a, b, c): return fma32(a, b, c)
+    def add_const(self, a, c): return np.float32(a) + np.float32(c)                              # |c2.z| + 1e-8f
+    def round_add(self, a, c): return np.float32(a) + np.float32(c)                              # cnt + 1e-6f
+    def le(self, a, b): return np.float32(a) <= np.float32(b)
+    def lt(self, a, b): return np.float32(a) < np.float32(b)
+    def ge(self, a, b): return np.float32(a) >= np.float32(b)
+    def gt(self, a, b): return np.float32(a) > np.float32(b)
+    def texel(self, v, cell_taint, cell_mag): return np.asarray(v, np.float32)
 
 
 class V:
@@ -220,6 +247,34 @@ class Cert:
     def abs(self, a): return V(np.abs(a.v), a.t)
     def sign(self, a): return V(np.sign(a.v), a.t)               # the sign of an exact value; a tainted one taints what it decides
 
+    # ---- what tests/exact_project.py adds
+    def val(self, a): return a.v
+    def floor(self, a): return V(np.floor(a.v), a.t)
+    def rint(self, a): return V(np.rint(a.v), a.t)
+    def fma(self, a, b, c): return self.add(self.mul(a, b), c, 'fma')       # product and sum both exact: fused or not, the same bits
+
+    def add_const(self, a, c):
+        """a + c for a constant c far below ulp(a): must round back to a (the one rounding the training projection is allowed)."""
+        s = f32(a.v + float(np.float32(c)))
+        return V(a.v, a.t | self._taint('constant not absorbed', (s != a.v) & ~a.t))
+
+    def round_add(self, a, c):
+        """fl32(a + c) of an exact a and a constant: one IEEE addition that no product feeds (nothing to fuse, no order to change) — the
+        rounded sum is the value the kernel holds, and counts as exact from here on (the mean fill's cnt + 1e-6f)."""
+        return V(f32(a.v + float(np.float32(c))), a.t)
+
+    def _cmp(self, a, b):
+        self._taint('comparison of an inexact value', (a.t | b.t) & np.isfinite(a.v) & np.isfinite(b.v))
+
+    def le(self, a, b): self._cmp(a, b); return a.v <= b.v
+    def lt(self, a, b): self._cmp(a, b); return a.v < b.v
+    def ge(self, a, b): self._cmp(a, b); return a.v >= b.v
+    def gt(self, a, b): self._cmp(a, b); return a.v > b.v
+
+    def texel(self, v, cell_taint, cell_mag):
+        """A fetched texel: exact, unless the cell it was fetched from was chosen by an inexact coordinate."""
+        return V(np.asarray(v, np.float64), np.broadcast_to(cell_taint, np.shape(v)).copy())
+
 
 BOUND_DOC = """Per-element bound of the general regime:  |got - ref| <= 2 (S + 9) 2^-24 mag (1 + 2^-10) + (S + 9) 2^-126.
 
@@ -244,8 +299,9 @@ below 2^-126, products of tiny transmittances), where a relative error bound doe
 
 class Mag:
     """float64 values with running magnitudes (BOUND_DOC)."""
-    def __init__(self, exp_rounds=4):
+    def __init__(self, exp_rounds=4, absorb=False):
         self.E = exp_rounds
+        self.absorb = absorb            # add_const rounds its sum to fp32 (exact_project's exact sets: the certified absorption of 1e-8f)
 
     def inp(self, x):
         x = np.asarray(x, np.float32).astype(np.float64)
@@ -291,6 +347,23 @@ class Mag:
     def cos(self, a): return V(np.cos(a.v), np.abs(np.cos(a.v)))
     def abs(self, a): return V(np.abs(a.v), a.t)
     def sign(self, a): return V(np.sign(a.v), np.abs(np.sign(a.v)))    # decided alike in both precisions (the input sets see to that)
+    # ---- what tests/exact_project.py adds.  floor: the integer carries no error of its own — a coordinate within rounding of an integer
+    # may fall into the neighbouring cell in fp32, where bilinear interpolation continues the same function; texel() therefore takes
+    # the largest |texel| of the cell's 4x4 neighbourhood as the magnitude of each of its taps.  Comparisons: decided on the values.
+    def val(self, a): return a.v
+    def floor(self, a): return V(np.floor(a.v), np.zeros(np.shape(a.v)))
+    def rint(self, a): return V(np.rint(a.v), np.zeros(np.shape(a.v)))
+    def fma(self, a, b, c): return self.add(self.mul(a, b), c)        # counted as its two unfused operations
+    def add_const(self, a, c):
+        s = a.v + float(np.float32(c))
+        return V(f32(s) if self.absorb else s, a.t + abs(float(np.float32(c))))
+
+    def round_add(self, a, c): return V(a.v + float(np.float32(c)), a.t + abs(float(np.float32(c))))
+    def le(self, a, b): return a.v <= b.v
+    def lt(self, a, b): return a.v < b.v
+    def ge(self, a, b): return a.v >= b.v
+    def gt(self, a, b): return a.v > b.v
+    def texel(self, v, cell_taint, cell_mag): return V(np.asarray(v, np.float64), np.broadcast_to(cell_mag, np.shape(v)).astype(np.float64))
 
 
 def bound(S, mag):
