@@ -388,6 +388,20 @@ int pnrf_ctx_profile_end(pnrf_ctx_t* ctx, float* ms, int* frames);
 int pnrf_composite_bwd(const float* raw, const float* z, const float* rays_d, int d_stride, const float* add,
                        const float* mul, const float* noise, float clamp, int white_bkgd, const float* d_rgb,
                        float* d_raw, float* d_z, float* d_add, float* d_mul, int64_t n, int s, void* stream);
+/* raw2outputs backward for the cotangents of ALL its outputs and of z itself: d_rgb dev [n,3], d_disp / d_acc / d_depth dev [n],
+ * d_weights dev [n,s], d_z_in dev [n,s] (a cotangent z receives from elsewhere; added into d_z, which must then be given).  Each
+ * may be NULL (= zeros), not all of them.  Inputs and outputs as pnrf_composite_bwd.  With w_s = alpha_s T_s the cotangent of w_s
+ * is  g_rgb . c_s - [white] sum g_rgb + G_depth z_s + G_acc + d_weights[s],  d_z[s] gains  w_s G_depth + d_z_in[s], and
+ * disp = 1 / max(1e-10, depth / acc) folds into the ray scalars: with r = depth / acc finite and > 1e-10,
+ * G_depth = d_depth - d_disp disp^2 / acc and G_acc = d_acc + d_disp disp^2 depth / acc^2; otherwise (the constant branch of the
+ * max, or acc == 0) d_disp contributes exact zeros — a deviation from autograd, which gives NaN at acc == 0.  depth and acc are
+ * summed again in pnrf_composite_fwd's order, so the branch is the one the forward took.  With d_rgb alone the call is
+ * pnrf_composite_bwd (the same launch: bit-identical).  Any s >= 1. */
+int pnrf_composite_bwd_maps(const float* raw, const float* z, const float* rays_d, int d_stride, const float* add,
+                            const float* mul, const float* noise, float clamp, int white_bkgd, const float* d_rgb,
+                            const float* d_disp, const float* d_acc, const float* d_weights, const float* d_depth,
+                            const float* d_z_in, float* d_raw, float* d_z, float* d_add, float* d_mul, int64_t n, int s,
+                            void* stream);
 /* Embedder.embed backward: d_x[n,3] from d_out[n, 3+6*n_freq] (run_nerf_helpers.py:666-671).  n_freq 0..16; at x = 0 the result
  * is exactly d_out[c] + sum_k 2^k d_out[sin_k] (tests/test_exact_heads_gpu.py pins it there, and forward and backward elsewhere
  * within a per-element bound, past the grid cap included). */
@@ -476,6 +490,29 @@ int pnrf_train_stage2_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_batch_t* batch
  * loss = img2mse(rgb_map1); gradients for the 12 NeRF layers only. */
 int pnrf_train_explore_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_batch_t* batch, int n_mult, int dir1, float* loss,
                                float* rgb_map1, void* stream);
+/* The joint iteration in two calls, for a loss of the caller's between them.  Every map is dev fp32; any pointer may be NULL.
+ * rgb_map1 / rgb_map0 / mm_rgb [n,3]: composited, refine-head and sampler-head colours; depth / acc / disp [n] and
+ * weights [n,8]: the other outputs of raw2outputs; z [n,8]: the refined, jittered sample depths the compositing used. */
+typedef struct pnrf_train_maps {
+  float *rgb_map1, *rgb_map0, *mm_rgb, *depth, *acc, *disp, *weights, *z;
+} pnrf_train_maps_t;
+typedef struct pnrf_train_cotangents {
+  const float *d_rgb_map1, *d_rgb_map0, *d_mm_rgb, *d_depth, *d_acc, *d_disp, *d_weights, *d_z;
+} pnrf_train_cotangents_t;
+/* Forward half of pnrf_train_stage2_fwd_bwd: the same launches up to and including the compositing (which here also writes
+ * disp, acc and depth), then the requested maps are copied out.  batch->target may be NULL and batch->a_mmrgb is ignored: the
+ * loss is the caller's.  Stage-1 even iterations: layout 1, eps 1e-6, clamp 10. */
+int pnrf_train_stage2_fwd(pnrf_trainer_t* t, const pnrf_train_batch_t* batch, const pnrf_train_maps_t* out, void* stream);
+/* Backward half, from the caller's cotangents of the maps (NULL = zeros; all NULL: PNRF_E_ARG), read in place: compositing
+ * backward for every map (pnrf_composite_bwd_maps; d_z enters there), the fine net, the refine head (d_rgb_map0), the refine
+ * net, the sampler head (d_mm_rgb), the sampler net.  Leaves the gradients of all 26 layers where the fused call leaves them
+ * (pnrf_trainer_read / _flat / _adam_step as after it); with d_rgb_map1 [, d_rgb_map0, d_mm_rgb] alone they are the fused
+ * call's, bit for bit.  It reads the batch copy the forward half staged in the trainer.
+ * State: valid only as the NEXT trainer call after a pnrf_train_stage2_fwd, on the same stream.  After any other iteration,
+ * pnrf_trainer_net_fwd_bwd, _adam_step, _write, _set_products, _set_dw_kernel or a first pnrf_train_stage2_bwd it returns
+ * PNRF_E_STATE, decided on the host before anything is launched.
+ * Both calls launch kernel by kernel whatever pnrf_trainer_set_graph says (a captured graph would hold the caller's pointers). */
+int pnrf_train_stage2_bwd(pnrf_trainer_t* t, const pnrf_train_cotangents_t* cotangents, void* stream);
 /* y = net(x); y.backward(dy) for ONE of the trainer's three nets, through the dispatch of the iterations (preparation launch, product kind,
  * weight-gradient tile choice, engine / chain / per-layer path chosen by row count, grouped weight-gradient launch).  Overwrites that net's
  * layer gradients only (kind 1 of pnrf_trainer_read).  Test-facing: the output gradient is the caller's, not the losses'.

@@ -92,6 +92,7 @@ SIGNATURES = {
     'pnrf_philox4x32_10': (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     # stage-2 training step
     'pnrf_composite_bwd': (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
+    'pnrf_composite_bwd_maps': (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
     'pnrf_posenc_bwd': (_i, [_p, _p, _p, _i64, _i, _p]),
     'pnrf_sampler_head_fwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     'pnrf_sampler_head_bwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
@@ -109,6 +110,8 @@ SIGNATURES = {
     'pnrf_trainer_flat': (_i, [_p, _i, C.POINTER(_p), C.POINTER(_i64)]),
     'pnrf_train_stage2_fwd_bwd': (_i, [_p, _p, _p, _p, _p]),
     'pnrf_train_explore_fwd_bwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    'pnrf_train_stage2_fwd': (_i, [_p, _p, _p, _p]),
+    'pnrf_train_stage2_bwd': (_i, [_p, _p, _p]),
     'pnrf_trainer_adam_step': (_i, [_p, _i, _f, _f, _f, _f, _f, _p]),
     'pnrf_trainer_net_fwd_bwd': (_i, [_p, _i, _p, _p, _i64, _i, _p, _p, _p, _p]),
 }
@@ -119,6 +122,18 @@ class TrainBatch(C.Structure):
     _fields_ = [('rays', _p), ('or_rays', _p), ('target', _p), ('img4', _p), ('poses', _p), ('K', _p), ('ref_nos', _p), ('jitter', _p),
                 ('raw_noise', _p), ('n', _i64), ('nv', _i), ('Hf', _i), ('Wf', _i), ('jitter_dir', _i), ('white_bkgd', _i), ('eps', _f),
                 ('a_mmrgb', _f), ('clamp', _f), ('layout', _i)]
+
+
+
+class TrainMaps(C.Structure):
+    """pnrf_train_maps_t: where pnrf_train_stage2_fwd copies each map (NULL: not wanted)."""
+    _fields_ = [(k, _p) for k in ('rgb_map1', 'rgb_map0', 'mm_rgb', 'depth', 'acc', 'disp', 'weights', 'z')]
+
+
+class TrainCotangents(C.Structure):
+    """pnrf_train_cotangents_t: the cotangent of each map for pnrf_train_stage2_bwd (NULL: zeros)."""
+    _fields_ = [('d_' + k, _p) for k in ('rgb_map1', 'rgb_map0', 'mm_rgb', 'depth', 'acc', 'disp', 'weights', 'z')]
+
 
 _lib = None
 

@@ -939,22 +939,37 @@ __global__ void refine_head_bwd_kernel(const float* __restrict__ y, const float*
 // recurrences over the lanes in sample order through v_readlane.  (A thread per ray walked 2 S memory latencies: 51 us for 4096 rays x 64
 // samples.)  d_raw is no scratch any more: alpha and T stay in registers (the chunks are walked from the last to the first for Q; for
 // S > 64 the transmittance at a chunk's start is recomputed from the chunks before it).
-__global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int d_stride,
+//
+// MAPS (pnrf_composite_bwd_maps): cotangents of the other outputs of raw2outputs and of z itself as well.  With w_s = alpha_s T_s every map is
+// linear in the weights, so they all fold into the per-sample cotangent of w_s,
+//   dws = g_rgb . c_s - [white] sum g_rgb + G_depth z_s + G_acc + g_w[s],      d z_s += w_s G_depth + d_z_in[s],
+// and disp = 1 / max(1e-10, depth / acc) folds into the two ray scalars: with r = depth / acc finite and > 1e-10
+//   G_depth = g_depth - g_disp disp^2 / acc,    G_acc = g_acc + g_disp disp^2 depth / acc^2,
+// otherwise (the constant branch of the max, or acc == 0 where autograd gives NaN) g_disp contributes exact zeros.  depth and acc are summed
+// again here (pass 0, ascending) with composite_kernel's operations in composite_kernel's order — ieee_* throughout, the MAPS instance forms
+// alpha that way too — so the branch is decided on the very values the forward wrote.  Everything after dws is the code below, shared.
+struct CompositeMaps { const float *d_disp, *d_acc, *d_w, *d_depth, *d_z_in; };
+template <bool MAPS>
+__device__ __forceinline__ void composite_bwd_body(const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int d_stride,
                                      const float* __restrict__ add, const float* __restrict__ mul, const float* __restrict__ noise, float clampv,
                                      int white_bkgd, const float* __restrict__ d_rgb, float* __restrict__ d_raw, float* __restrict__ d_z,
-                                     float* __restrict__ d_add, float* __restrict__ d_mul, int64_t n, int S) {
+                                     float* __restrict__ d_add, float* __restrict__ d_mul, int64_t n, int S, const CompositeMaps mp) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;                                                          // wave-uniform
   const float* d = rays_d + i * d_stride;
-  const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  const float g0 = d_rgb[i * 3], g1 = d_rgb[i * 3 + 1], g2 = d_rgb[i * 3 + 2];
+  float dn;
+  if constexpr (MAPS) dn = ieee_sqrt(ieee_add(ieee_add(ieee_mul(d[0], d[0]), ieee_mul(d[1], d[1])), ieee_mul(d[2], d[2])));
+  else dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  float g0, g1, g2;
+  if constexpr (MAPS) { g0 = d_rgb ? d_rgb[i * 3] : 0.f; g1 = d_rgb ? d_rgb[i * 3 + 1] : 0.f; g2 = d_rgb ? d_rgb[i * 3 + 2] : 0.f; }
+  else { g0 = d_rgb[i * 3]; g1 = d_rgb[i * 3 + 1]; g2 = d_rgb[i * 3 + 2]; }
   const float gsum = white_bkgd ? (g0 + g1 + g2) : 0.f;                         // rgb_map += 1 - sum_s w_s
   const bool clamped = clampv > 0.f;
   auto lane_val = [](float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
   const int nchunks = (S + 63) / 64;
   // per-sample quantities of one chunk (this lane's sample): everything both passes need
-  struct Smp { float r0, r1, r2, raw3, sg, dist, al, a, ml; bool on; int64_t e; int s; };
+  struct Smp { float r0, r1, r2, raw3, sg, dist, al, a, ml, zc; bool on; int64_t e; int s; };
   auto load = [&](int c0) {
     Smp q;
     const int m = S - c0 < 64 ? S - c0 : 64;
@@ -969,10 +984,16 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
     if (add) sg += add[q.e];
     q.sg = sg;
     const float zc = z[q.e], zn = (q.on && q.s + 1 < S) ? z[q.e + 1] : 0.f;
+    q.zc = zc;
     q.dist = ((q.s + 1 < S) ? (zn - zc) : 1e10f) * dn;
-    q.a = 1.f - expf(-fmaxf(sg, 0.f) * q.dist);
     q.ml = mul ? mul[q.e] : 1.f;
-    q.al = mul ? q.a * fmaxf(q.ml, 0.f) : q.a;
+    if constexpr (MAPS) {
+      q.a = ieee_sub(1.f, expf(ieee_mul(-fmaxf(sg, 0.f), q.dist)));
+      q.al = mul ? ieee_mul(q.a, fmaxf(q.ml, 0.f)) : q.a;
+    } else {
+      q.a = 1.f - expf(-fmaxf(sg, 0.f) * q.dist);
+      q.al = mul ? q.a * fmaxf(q.ml, 0.f) : q.a;
+    }
     return q;
   };
   // T at the start of chunk c = the product over the chunks before it, in sample order (one chunk for S <= 64: nothing to do)
@@ -985,8 +1006,33 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
     }
     return T;
   };
+  // pass 0 (MAPS, ascending): depth = sum w z and acc = sum w as composite_kernel sums them, then the two ray scalars
+  float Gd = 0.f, Ga = 0.f;
+  if constexpr (MAPS) {
+    Gd = mp.d_depth ? mp.d_depth[i] : 0.f;
+    Ga = mp.d_acc ? mp.d_acc[i] : 0.f;
+    const float gdisp = mp.d_disp ? mp.d_disp[i] : 0.f;
+    if (mp.d_disp) {                                                           // wave-uniform
+      float T = 1.f, sd = 0.f, sa = 0.f;
+      for (int c0 = 0; c0 < S; c0 += 64) {
+        const int m = S - c0 < 64 ? S - c0 : 64;
+        const Smp q = load(c0);
+        const float x = ieee_add(ieee_sub(1.f, q.al), 1e-10f);
+        float Tl = 0.f;
+        for (int j = 0; j < m; ++j) { Tl = lane == j ? T : Tl; T = ieee_mul(T, lane_val(x, j)); }
+        const float w = ieee_mul(q.al, Tl), cdv = ieee_mul(w, q.zc);
+        for (int j = 0; j < m; ++j) { sd = ieee_add(sd, lane_val(cdv, j)); sa = ieee_add(sa, lane_val(w, j)); }
+      }
+      const float r = ieee_div(sd, sa);
+      if (r > 1e-10f && r < INFINITY) {                                        // false for NaN (0 / 0) and inf too: exact zeros from g_disp
+        const float disp = ieee_div(1.f, r), k = gdisp * disp * disp / sa;
+        Gd -= k;
+        Ga += k * sd / sa;
+      }
+    }
+  }
   // pass 2 (descending)
-  float Q = 0.f, dd_next = 0.f;
+  float Q = 0.f, dd_next = 0.f, w_next = 0.f;
   for (int c = nchunks - 1; c >= 0; --c) {
     const int c0 = 64 * c, m = S - c0 < 64 ? S - c0 : 64;
     const Smp q = load(c0);
@@ -997,7 +1043,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
     const bool in0 = !clamped || fabsf(r0) <= clampv, in1 = !clamped || fabsf(r1) <= clampv, in2 = !clamped || fabsf(r2) <= clampv;
     if (clamped) { r0 = fminf(fmaxf(r0, -clampv), clampv); r1 = fminf(fmaxf(r1, -clampv), clampv); r2 = fminf(fmaxf(r2, -clampv), clampv); }
     const float c0v = sigmoid_f(r0), c1v = sigmoid_f(r1), c2v = sigmoid_f(r2);
-    const float dws = g0 * c0v + g1 * c1v + g2 * c2v - gsum;
+    float dws = g0 * c0v + g1 * c1v + g2 * c2v - gsum;
+    if constexpr (MAPS) dws = dws + Gd * q.zc + Ga + (mp.d_w ? mp.d_w[q.e] : 0.f);
     // Q_s (the value the thread-per-ray loop had when it reached sample s) for this lane, then Q <- dws al + x Q, sample by sample from the top
     float Ql = 0.f;
     for (int j = m - 1; j >= 0; --j) {
@@ -1016,6 +1063,12 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
     float dd_up = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + 1) & 63) << 2, __float_as_int(ddist)));
     if (lane == m - 1) dd_up = dd_next;
     dd_next = lane_val(ddist, 0);
+    float w_up = 0.f;                                                          // MAPS: w_{s+1}, for the d_z this lane writes
+    if constexpr (MAPS) {
+      w_up = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + 1) & 63) << 2, __float_as_int(w)));
+      if (lane == m - 1) w_up = w_next;
+      w_next = lane_val(w, 0);
+    }
     if (q.on) {
       float4 o;
       o.x = in0 ? g0 * w * c0v * (1.f - c0v) : 0.f;
@@ -1025,12 +1078,29 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
       *(float4*)(d_raw + q.e * 4) = o;
       if (d_mul) d_mul[q.e] = (mul && q.ml > 0.f) ? dal * q.a : 0.f;
       if (d_add) d_add[q.e] = add ? dsg : 0.f;
-      if (d_z) {
+      if constexpr (MAPS) {
+        if (d_z) {
+          if (q.s + 1 < S) d_z[q.e + 1] = ddist - dd_up + w_up * Gd + (mp.d_z_in ? mp.d_z_in[q.e + 1] : 0.f);
+          if (q.s == 0) d_z[q.e] = -ddist + w * Gd + (mp.d_z_in ? mp.d_z_in[q.e] : 0.f);
+        }
+      } else if (d_z) {
         if (q.s + 1 < S) d_z[q.e + 1] = ddist - dd_up;
         if (q.s == 0) d_z[q.e] = -ddist;
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d, int d_stride,
+                                     const float* __restrict__ add, const float* __restrict__ mul, const float* __restrict__ noise, float clampv,
+                                     int white_bkgd, const float* __restrict__ d_rgb, float* __restrict__ d_raw, float* __restrict__ d_z,
+                                     float* __restrict__ d_add, float* __restrict__ d_mul, int64_t n, int S) {
+  composite_bwd_body<false>(raw, z, rays_d, d_stride, add, mul, noise, clampv, white_bkgd, d_rgb, d_raw, d_z, d_add, d_mul, n, S, CompositeMaps{});
+}
+__global__ __launch_bounds__(256) void composite_bwd_maps_kernel(const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d,
+                                     int d_stride, const float* __restrict__ add, const float* __restrict__ mul, const float* __restrict__ noise,
+                                     float clampv, int white_bkgd, const float* __restrict__ d_rgb, float* __restrict__ d_raw, float* __restrict__ d_z,
+                                     float* __restrict__ d_add, float* __restrict__ d_mul, int64_t n, int S, const CompositeMaps mp) {
+  composite_bwd_body<true>(raw, z, rays_d, d_stride, add, mul, noise, clampv, white_bkgd, d_rgb, d_raw, d_z, d_add, d_mul, n, S, mp);
 }
 
 // ------------------------------------------------------------------------------------------ losses, Adam
@@ -1203,7 +1273,16 @@ struct pnrf_trainer {
   DwhGroupArgs grp;                              // split-fp16 weight gradients waiting for the iteration's one grouped launch (flush_dw_group): the 256-wide
   int grp_blocks = 0;                            // layers of all three nets; their gradient / activation buffers stay untouched until then
   float* d_hs[6] = {};                           // the sampler net's hidden gradients (d_hk holds the refine net's until the grouped launch)
+  // the joint iteration in two calls (pnrf_train_stage2_fwd / _bwd): the per-ray maps the fused call does not keep, and what the backward
+  // half needs to know about the forward half before it
+  float *m_disp = nullptr, *m_acc = nullptr, *m_depth = nullptr;
+  bool split_open = false;                       // the most recent trainer call was a pnrf_train_stage2_fwd: its activations are still whole
+  const char* split_closed_by = "no pnrf_train_stage2_fwd has run";
+  hipStream_t split_stream = nullptr;
+  pnrf_train_batch_t split_bt = {};              // that call's batch, pointing at the staged copies
 };
+// every trainer call that overwrites activations, gradients or parameters, or changes the kernel selection, ends a forward half's validity
+static inline void close_split(pnrf_trainer* t, const char* who) { t->split_open = false; t->split_closed_by = who; }
 
 namespace {
 
@@ -1559,6 +1638,28 @@ extern "C" int pnrf_composite_bwd(const float* raw, const float* z, const float*
   return 0;
 }
 
+// raw2outputs backward for the cotangents of all five outputs and of z (composite_bwd_body<true>).  With d_rgb alone it IS pnrf_composite_bwd: the
+// same launch of the same kernel.
+extern "C" int pnrf_composite_bwd_maps(const float* raw, const float* z, const float* rays_d, int d_stride, const float* add, const float* mul,
+                                       const float* noise, float clampv, int white_bkgd, const float* d_rgb, const float* d_disp, const float* d_acc,
+                                       const float* d_weights, const float* d_depth, const float* d_z_in, float* d_raw, float* d_z, float* d_add,
+                                       float* d_mul, int64_t n, int s, void* stream) {
+  PNRF_REQUIRE(n >= 0 && s >= 1 && d_stride >= 3, PNRF_E_ARG, "pnrf_composite_bwd_maps: bad sizes");
+  if (n == 0) return 0;
+  PNRF_REQUIRE(raw && z && rays_d && d_raw, PNRF_E_ARG, "pnrf_composite_bwd_maps: null pointer");
+  PNRF_REQUIRE(d_rgb || d_disp || d_acc || d_weights || d_depth || d_z_in, PNRF_E_ARG, "pnrf_composite_bwd_maps: every cotangent is NULL");
+  PNRF_REQUIRE((((uintptr_t)raw | (uintptr_t)d_raw) & 15) == 0, PNRF_E_ARG, "pnrf_composite_bwd_maps: raw and d_raw must be 16-byte aligned (16-byte loads / stores per sample)");
+  PNRF_REQUIRE((add == nullptr) == (mul == nullptr), PNRF_E_ARG, "pnrf_composite_bwd_maps: add and mul go together");
+  PNRF_REQUIRE(!d_z_in || d_z, PNRF_E_ARG, "pnrf_composite_bwd_maps: d_z_in is added into d_z, which is NULL");
+  if (!(d_disp || d_acc || d_weights || d_depth || d_z_in))
+    return pnrf_composite_bwd(raw, z, rays_d, d_stride, add, mul, noise, clampv, white_bkgd, d_rgb, d_raw, d_z, d_add, d_mul, n, s, stream);
+  const CompositeMaps mp = {d_disp, d_acc, d_weights, d_depth, d_z_in};
+  hipLaunchKernelGGL(composite_bwd_maps_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw, z, rays_d, d_stride, add, mul, noise,
+                     clampv, white_bkgd, d_rgb, d_raw, d_z, d_add, d_mul, n, s, mp);
+  PNRF_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int pnrf_posenc_bwd(const float* x, const float* d_out, float* d_x, int64_t n, int n_freq, void* stream) {
   PNRF_REQUIRE(n >= 0 && n_freq >= 0 && n_freq <= 16 && (n == 0 || (x && d_out && d_x)), PNRF_E_ARG, "pnrf_posenc_bwd: bad arguments");
   if (n == 0) return 0;
@@ -1726,6 +1827,7 @@ static int trainer_init(pnrf_trainer* t, const float* const* W, const float* con
   PNRF_HIP(hipMemset(t->n_c5, 0, (size_t)Rp * LD_C5 * 4)); PNRF_HIP(hipMemset(t->d_c5, 0, (size_t)Rp * LD_C5 * 4));
   PNRF_HIP(hipMemset(t->n_cv, 0, (size_t)Rp * LD_CV * 4)); PNRF_HIP(hipMemset(t->d_cv, 0, (size_t)Rp * LD_CV * 4));
   T_ALLOC(t->st_rays, N * 11); T_ALLOC(t->st_or_rays, N * 11); T_ALLOC(t->st_target, N * 3); T_ALLOC(t->st_ref_nos, N * 4); T_ALLOC(t->st_jitter, R); T_ALLOC(t->st_noise, R);
+  T_ALLOC(t->m_disp, N); T_ALLOC(t->m_acc, N); T_ALLOC(t->m_depth, N);
   T_ALLOC(t->loss, 8);                              // [total, mse x 3, completion counter of losses_kernel]
   PNRF_HIP(hipMemset(t->loss, 0, 32));
   {   // one slice of split-K partials per layer and iteration, each at its largest
@@ -1777,6 +1879,7 @@ extern "C" int pnrf_trainer_write(pnrf_trainer_t* t, int kind, int layer, const 
   PNRF_REQUIRE(t && kind >= 0 && kind <= 5 && layer >= 0 && layer < N_LAYERS, PNRF_E_ARG, "pnrf_trainer_write: bad kind / layer");
   float* base = kind == 0 ? t->P : kind == 1 ? t->G : kind == 2 ? t->M : kind == 3 ? t->V : kind == 4 ? t->M2 : t->V2;
   const TLin& l = t->L[layer];
+  close_split(t, "pnrf_trainer_write");
   if (W) PNRF_HIP(hipMemcpyAsync(base + l.w, W, (size_t)l.in * l.out * 4, hipMemcpyDefault, (hipStream_t)stream));
   if (b) PNRF_HIP(hipMemcpyAsync(base + l.b, b, (size_t)l.out * 4, hipMemcpyDefault, (hipStream_t)stream));
   PNRF_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -1806,6 +1909,7 @@ extern "C" int pnrf_trainer_set_dw_kernel(pnrf_trainer_t* t, int tile, int64_t m
   PNRF_REQUIRE(t && (tile == 0 || tile == 64 || tile == 128 || tile == 255 || tile == 256) && min_rows_128 >= 0, PNRF_E_ARG,
                "pnrf_trainer_set_dw_kernel: tile must be 0, 64, 128 (or 256 / 255: the wide grouped tiles on / off)");
   drop_graphs(t);
+  close_split(t, "pnrf_trainer_set_dw_kernel");
   if (tile == 255 || tile == 256) {
     t->dw_wide_min_rows = tile == 255 ? INT64_MAX : (min_rows_128 > 0 ? min_rows_128 : 1);
     return 0;
@@ -1834,6 +1938,7 @@ extern "C" int pnrf_trainer_set_step(pnrf_trainer_t* t, int64_t step, int64_t st
 extern "C" int pnrf_trainer_adam_step(pnrf_trainer_t* t, int which, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
   PNRF_REQUIRE(t && (which == 0 || which == 1) && lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, PNRF_E_ARG,
                "pnrf_trainer_adam_step: bad arguments");
+  close_split(t, "pnrf_trainer_adam_step");
   int64_t& st = which == 0 ? t->step : t->step2;
   st += 1;
   const double bc1 = 1.0 - pow((double)beta1, (double)st), bc2 = 1.0 - pow((double)beta2, (double)st);
@@ -2121,15 +2226,50 @@ static int prepare_iteration(pnrf_trainer* t, const pnrf_train_batch_t* bt, int6
 // iterations (base.py:554-761 with train_sampler=True, :941-958): layout 1, eps 1e-6, clamp 10, no jitter / noise, a_mmrgb 1.
 // Gradients of all 26 layers are left in the trainer (pnrf_trainer_read kind 1); loss dev [4] = {total, mse(rgb_map1),
 // mse(rgb_map0), mse(mm_rgb)}; rgb_out dev [n,3] or NULL.
-static int stage2_body(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, hipStream_t s) {
+// The iteration is two halves around its loss: stage2_forward leaves every activation and map in the trainer, stage2_backward starts from the
+// cotangents of the maps.  The fused call runs them around losses_kernel (cot == NULL: the loss kernel's d_rgb_map / d_rgb0 / d_mmrgb, the
+// launches it always had); pnrf_train_stage2_fwd / _bwd run them as two calls around the caller's loss.
+static int stage2_forward(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, bool all_maps, hipStream_t s) {
   void* stream = (void*)s;
-  const int64_t N = bt->n, R = 8 * bt->n;
-  // ---------------- forward
+  const int64_t N = bt->n;
   T_RC(sampler_refine_forward(t, bt, s));
   T_RC(pnrf_refine_head_fwd(t->r_y, bt->rays, t->depth_sorted, bt->jitter, bt->jitter_dir, t->z_pre, t->z, t->pts, t->rgb0, N, stream));   // :635-668
   T_RC(nerf_forward(t, bt, 8, s));
-  T_RC(pnrf_composite_fwd(t->raw, t->z, bt->rays + 3, 11, t->add_s, t->mul_s, bt->raw_noise, bt->clamp, bt->white_bkgd, t->rgb_map, nullptr, nullptr,
-                          t->wts, nullptr, N, 8, stream));                                                            // :674
+  T_RC(pnrf_composite_fwd(t->raw, t->z, bt->rays + 3, 11, t->add_s, t->mul_s, bt->raw_noise, bt->clamp, bt->white_bkgd, t->rgb_map,
+                          all_maps ? t->m_disp : nullptr, all_maps ? t->m_acc : nullptr, t->wts, all_maps ? t->m_depth : nullptr, N, 8, stream));   // :674
+  return 0;
+}
+
+static int stage2_backward(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, const pnrf_train_cotangents_t* cot, bool aux, hipStream_t s) {
+  void* stream = (void*)s;
+  const int64_t N = bt->n, R = 8 * bt->n;
+  const float *d_rgb0 = aux ? t->d_rgb0 : nullptr, *d_mmrgb = aux ? t->d_mmrgb : nullptr;
+  if (!cot) {
+    T_RC(pnrf_composite_bwd(t->raw, t->z, bt->rays + 3, 11, t->add_s, t->mul_s, bt->raw_noise, bt->clamp, bt->white_bkgd, t->d_rgb_map, t->d_raw, t->d_z,
+                            t->d_add, t->d_mul, N, 8, stream));
+  } else {
+    d_rgb0 = cot->d_rgb_map0; d_mmrgb = cot->d_mm_rgb;
+    const float* d_rgb = cot->d_rgb_map1;
+    if (!(d_rgb || cot->d_disp || cot->d_acc || cot->d_weights || cot->d_depth || cot->d_z)) {   // nothing reaches the compositing: its
+      PNRF_HIP(hipMemsetAsync(t->d_rgb_map, 0, (size_t)N * 3 * 4, s));                             // backward of an all-zero d rgb_map
+      d_rgb = t->d_rgb_map;
+    }
+    T_RC(pnrf_composite_bwd_maps(t->raw, t->z, bt->rays + 3, 11, t->add_s, t->mul_s, bt->raw_noise, bt->clamp, bt->white_bkgd, d_rgb, cot->d_disp,
+                                 cot->d_acc, cot->d_weights, cot->d_depth, cot->d_z, t->d_raw, t->d_z, t->d_add, t->d_mul, N, 8, stream));
+  }
+  T_RC(nerf_backward(t, R, true, s));
+  T_RC(pnrf_refine_head_bwd(t->r_y, bt->rays, t->depth_sorted, t->z_pre, bt->jitter, bt->jitter_dir, t->d_pts, t->d_z, d_rgb0, t->d_ry, t->d_depth, N,
+                            stream));
+  T_RC(elu_net_backward(t, L_R, t->d_ry, 35, t->r_h, t->refine_in, 144, N, s));
+  T_RC(pnrf_sampler_head_bwd(t->s_y, bt->rays, t->sort_idx, t->d_depth, t->d_add, t->d_mul, d_mmrgb, t->d_sy, N, stream));
+  T_RC(elu_net_backward(t, L_S, t->d_sy, 27, t->s_h, t->mm_input, 288, N, s));
+  return 0;
+}
+
+static int stage2_body(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, hipStream_t s) {
+  const int64_t N = bt->n;
+  // ---------------- forward
+  T_RC(stage2_forward(t, bt, false, s));
   // ---------------- losses (:861-866)
   const bool aux = bt->a_mmrgb > 0.f;
   {
@@ -2139,15 +2279,7 @@ static int stage2_body(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, hipStrea
   }
   PNRF_LAUNCH_CHECK();
   // ---------------- backward
-  T_RC(pnrf_composite_bwd(t->raw, t->z, bt->rays + 3, 11, t->add_s, t->mul_s, bt->raw_noise, bt->clamp, bt->white_bkgd, t->d_rgb_map, t->d_raw, t->d_z,
-                          t->d_add, t->d_mul, N, 8, stream));
-  T_RC(nerf_backward(t, R, true, s));
-  T_RC(pnrf_refine_head_bwd(t->r_y, bt->rays, t->depth_sorted, t->z_pre, bt->jitter, bt->jitter_dir, t->d_pts, t->d_z, aux ? t->d_rgb0 : nullptr, t->d_ry,
-                            t->d_depth, N, stream));
-  T_RC(elu_net_backward(t, L_R, t->d_ry, 35, t->r_h, t->refine_in, 144, N, s));
-  T_RC(pnrf_sampler_head_bwd(t->s_y, bt->rays, t->sort_idx, t->d_depth, t->d_add, t->d_mul, aux ? t->d_mmrgb : nullptr, t->d_sy, N, stream));
-  T_RC(elu_net_backward(t, L_S, t->d_sy, 27, t->s_h, t->mm_input, 288, N, s));
-  return 0;
+  return stage2_backward(t, bt, nullptr, aux, s);
 }
 
 // Stage-1 odd iteration (base.py:554-761 with train_sampler=False, :929-940): sampler and refine nets run without gradient,
@@ -2185,6 +2317,7 @@ static int run_iteration(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, int ki
                          hipStream_t caller, Body body_) {
   const int64_t N = bt->n;
   hipStream_t s = caller;
+  close_split(t, kind == 0 ? "pnrf_train_stage2_fwd_bwd" : "pnrf_train_explore_fwd_bwd");
   const bool hop = t->use_graph && caller == nullptr;          // the legacy default stream cannot be captured
   if (hop) {
     s = t->own_stream;
@@ -2252,6 +2385,49 @@ extern "C" int pnrf_train_explore_fwd_bwd(pnrf_trainer_t* t, const pnrf_train_ba
                        [&](const pnrf_train_batch_t* b, hipStream_t st) { return explore_body(t, b, n_mult, dir1, st); });
 }
 
+// The joint iteration in two calls, for a loss of the caller's (include/pronerf_hip.h).  _fwd: prepare_iteration with the batch staged, the forward
+// half, the requested maps copied out; the trainer remembers the staged batch and the stream.  _bwd: begin_dw, the backward half from the caller's
+// cotangents (read in place: nothing is captured, so they need no staging), flush_dw_reduce.  Kernel by kernel always: a captured graph would have
+// to hold the caller's cotangent pointers.  Host-side state only decides validity, before any launch.
+extern "C" int pnrf_train_stage2_fwd(pnrf_trainer_t* t, const pnrf_train_batch_t* bt, const pnrf_train_maps_t* out, void* stream) {
+  PNRF_REQUIRE(t && bt && out, PNRF_E_ARG, "pnrf_train_stage2_fwd: null pointer");
+  float probe = 0.f;                                           // check_batch wants a loss and a target: this call has neither to give
+  pnrf_train_batch_t chk = *bt;
+  if (!chk.target) chk.target = &probe;
+  T_RC(check_batch(t, &chk, &probe, 8, "pnrf_train_stage2_fwd"));
+  hipStream_t s = (hipStream_t)stream;
+  close_split(t, "a pnrf_train_stage2_fwd that failed");
+  const int64_t N = bt->n;
+  pnrf_train_batch_t in = *bt;
+  if (!in.target) in.target = t->st_target;                    // the staging launch copies a target: without one, the staged copy onto itself
+  T_RC(prepare_iteration(t, &in, N * 8, 8, s));
+  pnrf_train_batch_t b = *bt;
+  b.rays = t->st_rays; b.or_rays = t->st_or_rays; b.target = t->st_target; b.ref_nos = t->st_ref_nos;
+  b.jitter = bt->jitter ? t->st_jitter : nullptr; b.raw_noise = bt->raw_noise ? t->st_noise : nullptr;
+  T_RC(stage2_forward(t, &b, true, s));
+  const struct { float* dst; const float* src; int64_t count; } copies[8] = {
+      {out->rgb_map1, t->rgb_map, N * 3}, {out->rgb_map0, t->rgb0, N * 3}, {out->mm_rgb, t->mm_rgb, N * 3}, {out->depth, t->m_depth, N},
+      {out->acc, t->m_acc, N},            {out->disp, t->m_disp, N},       {out->weights, t->wts, N * 8},   {out->z, t->z, N * 8}};
+  for (const auto& c : copies)
+    if (c.dst) PNRF_HIP(hipMemcpyAsync(c.dst, c.src, (size_t)c.count * 4, hipMemcpyDeviceToDevice, s));
+  t->split_bt = b; t->split_stream = s; t->split_open = true;
+  return 0;
+}
+
+extern "C" int pnrf_train_stage2_bwd(pnrf_trainer_t* t, const pnrf_train_cotangents_t* cot, void* stream) {
+  PNRF_REQUIRE(t && cot, PNRF_E_ARG, "pnrf_train_stage2_bwd: null pointer");
+  PNRF_REQUIRE(cot->d_rgb_map1 || cot->d_rgb_map0 || cot->d_mm_rgb || cot->d_depth || cot->d_acc || cot->d_disp || cot->d_weights || cot->d_z, PNRF_E_ARG,
+               "pnrf_train_stage2_bwd: every cotangent is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  PNRF_REQUIRE(t->split_open, PNRF_E_STATE,
+               "pnrf_train_stage2_bwd: valid only as the next trainer call after pnrf_train_stage2_fwd, but the most recent one was: %s", t->split_closed_by);
+  PNRF_REQUIRE(s == t->split_stream, PNRF_E_STATE, "pnrf_train_stage2_bwd: called on another stream than the pnrf_train_stage2_fwd before it");
+  close_split(t, "pnrf_train_stage2_bwd (a forward half is good for one backward)");
+  begin_dw(t);
+  T_RC(stage2_backward(t, &t->split_bt, cot, false, s));
+  return flush_dw_reduce(t, s);
+}
+
 // y = net(x); y.backward(dy) for one of the three nets through the iterations' own dispatch (prepare_iteration, product kind, engine / chain /
 // per-layer path by row count, grouped weight gradients): the net's inputs and output gradient go into the buffers the iterations use for them,
 // its layer gradients are overwritten, the other nets' are left alone.  A test-facing operator (include/pronerf_hip.h).
@@ -2262,6 +2438,7 @@ extern "C" int pnrf_trainer_net_fwd_bwd(pnrf_trainer_t* t, int net, const float*
   PNRF_REQUIRE(n >= 1 && n <= t->max_rays, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: n = %lld outside [1, max_rays = %lld]", (long long)n,
                (long long)t->max_rays);
   hipStream_t s = (hipStream_t)stream;
+  close_split(t, "pnrf_trainer_net_fwd_bwd");
   if (net < 2) {
     PNRF_REQUIRE(!d_pts, PNRF_E_ARG, "pnrf_trainer_net_fwd_bwd: d_pts belongs to the fine net (net 2)");
     const int first = net == 0 ? L_S : L_R, in0 = net == 0 ? 288 : 144, out = net == 0 ? 27 : 35;
@@ -2307,6 +2484,7 @@ extern "C" int pnrf_trainer_set_products(pnrf_trainer_t* t, int kind) {
   PNRF_REQUIRE(t && kind >= 0 && kind <= 3, PNRF_E_ARG,
                "pnrf_trainer_set_products: kind 0 (split fp16), 1 (fp32), 2 (split fp16, one launch per layer) or 3 (split fp16, 64-row layer chains)");
   drop_graphs(t);
+  close_split(t, "pnrf_trainer_set_products");
   t->use_f16 = kind != 1;
   t->nerf_fwd = kind == 1 ? 0 : kind;
   params_changed(t);                               // (also the fp32 kernels' gapped copy of the skip layer's weights is written with the planes)

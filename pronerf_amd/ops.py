@@ -789,6 +789,28 @@ def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0
     return d_raw, d_z, d_add, d_mul
 
 
+def composite_bwd_maps(raw, z, rays_d, d_rgb=None, d_disp=None, d_acc=None, d_weights=None, d_depth=None, d_z=None, add=None, mul=None, noise=None,
+                       clamp=0.0, white_bkgd=False):
+    """raw2outputs backward for the cotangents of all its outputs — d_rgb [n, 3], d_disp / d_acc / d_depth [n], d_weights [n, s] — and one that z
+    receives from elsewhere (d_z [n, s], added into the returned d_z); None = zeros, not all of them -> (d_raw, d_z, d_add, d_mul) as
+    composite_bwd.  A ray with acc == 0 (or depth / acc <= 1e-10) gets exact zeros from d_disp (pnrf_composite_bwd_maps)."""
+    raw = _chk(raw, 'raw', (4,)); z = _chk(z, 'z_vals'); rays_d, d_stride = _chk_rows(rays_d, 'rays_d', 3)
+    n, s = z.shape
+    cot = [None if t is None else _chk(t, name, tail) for t, name, tail in
+           ((d_rgb, 'd_rgb', (n, 3)), (d_disp, 'd_disp', (n,)), (d_acc, 'd_acc', (n,)), (d_weights, 'd_weights', (n, s)), (d_depth, 'd_depth', (n,)),
+            (d_z, 'd_z', (n, s)))]
+    add = None if add is None else _chk(add, 'mm_density_add')
+    mul = None if mul is None else _chk(mul, 'mm_density_mul')
+    noise = None if noise is None else _chk(noise, 'noise')
+    d_raw = torch.empty_like(raw); o_z = torch.empty_like(z)
+    d_add = None if add is None else torch.empty_like(z)
+    d_mul = None if mul is None else torch.empty_like(z)
+    check(_lib.load().pnrf_composite_bwd_maps(_ptr(raw), _ptr(z), _ptr(rays_d), d_stride, _ptr(add), _ptr(mul), _ptr(noise), float(clamp),
+                                              int(bool(white_bkgd)), *[_ptr(c) for c in cot], _ptr(d_raw), _ptr(o_z), _ptr(d_add), _ptr(d_mul), n, s,
+                                              _stream()), 'pnrf_composite_bwd_maps')
+    return d_raw, o_z, d_add, d_mul
+
+
 def posenc_bwd(x, d_out, n_freq):
     x = _chk(x, 'x', (3,)); d_out = _chk(d_out, 'd_out', (3 + 6 * n_freq,))
     d_x = torch.empty_like(x)
@@ -930,7 +952,7 @@ class Trainer:
         check(_lib.load().pnrf_trainer_set_step(self.handle, int(step), int(step_nerf)), 'pnrf_trainer_set_step')
 
     def _batch(self, rays, or_rays, target, img4, poses, K, ref_nos, jitter, jitter_dir, raw_noise, white_bkgd, eps, a_mmrgb, clamp, layout, S):
-        rays = _chk(rays, 'rays', (11,)); or_rays = _chk(or_rays, 'or_rays', (11,)); target = _chk(target, 'target', (3,))
+        rays = _chk(rays, 'rays', (11,)); or_rays = _chk(or_rays, 'or_rays', (11,)); target = None if target is None else _chk(target, 'target', (3,))
         img4 = _chk(img4, 'img4', (4,)); poses = _chk(poses, 'poses', (3, 4)); K = _chk(K, 'K', (3, 3))
         if ref_nos.dtype != torch.int64 or not ref_nos.is_cuda or tuple(ref_nos.shape) != (rays.shape[0], 4):
             raise PnrfError('ref_nos: expected an int64 GPU tensor [n, 4]')
@@ -938,7 +960,7 @@ class Trainer:
         jitter = None if jitter is None else _chk(jitter, 'jitter', (S,))
         raw_noise = None if raw_noise is None else _chk(raw_noise, 'raw_noise', (S,))
         keep = (rays, or_rays, target, img4, poses, K, ref_nos, jitter, raw_noise)          # alive until the call returns
-        bt = _lib.TrainBatch(rays=rays.data_ptr(), or_rays=or_rays.data_ptr(), target=target.data_ptr(), img4=img4.data_ptr(), poses=poses.data_ptr(),
+        bt = _lib.TrainBatch(rays=rays.data_ptr(), or_rays=or_rays.data_ptr(), target=None if target is None else target.data_ptr(), img4=img4.data_ptr(), poses=poses.data_ptr(),
                              K=K.data_ptr(), ref_nos=ref_nos.data_ptr(), jitter=None if jitter is None else jitter.data_ptr(),
                              raw_noise=None if raw_noise is None else raw_noise.data_ptr(), n=rays.shape[0], nv=img4.shape[0], Hf=img4.shape[1],
                              Wf=img4.shape[2], jitter_dir=int(jitter_dir), white_bkgd=int(bool(white_bkgd)), eps=float(eps), a_mmrgb=float(a_mmrgb),
@@ -956,6 +978,56 @@ class Trainer:
         with torch.cuda.device(dev):
             check(_lib.load().pnrf_train_stage2_fwd_bwd(self.handle, C.byref(bt), _ptr(loss), _ptr(rgb), _stream()), 'pnrf_train_stage2_fwd_bwd')
         return loss, rgb
+
+    # the maps of pnrf_train_maps_t, in the struct's order: name -> trailing shape after the ray count
+    MAPS = {'rgb_map1': (3,), 'rgb_map0': (3,), 'mm_rgb': (3,), 'depth': (), 'acc': (), 'disp': (), 'weights': (8,), 'z': (8,)}
+
+    @property
+    def anchor(self):
+        """A zero-dim leaf with requires_grad: the differentiable input ``autograd.render_train`` hangs the trainer's maps on (the parameters
+        live in the trainer, not in torch)."""
+        if getattr(self, '_anchor', None) is None:
+            self._anchor = torch.zeros((), device=self.device, dtype=f32, requires_grad=True)
+        return self._anchor
+
+    def forward(self, rays, or_rays, img4, poses, K, ref_nos, jitter=None, jitter_dir=1, raw_noise=None, white_bkgd=False, eps=1e-5, clamp=0.0,
+                layout=0, want=None):
+        """Forward half of the joint iteration (pnrf_train_stage2_fwd) -> dict of fresh tensors keyed by ``Trainer.MAPS`` (want: the names to
+        return; None = all).  ``backward`` must be the next call on this trainer, on the same stream.  Always kernel by kernel (set_graph does
+        not apply)."""
+        want = tuple(self.MAPS) if want is None else tuple(want)
+        for k in want:
+            if k not in self.MAPS:
+                raise PnrfError(f'Trainer.forward: unknown map {k!r} (one of {list(self.MAPS)})')
+        bt, keep = self._batch(rays, or_rays, None, img4, poses, K, ref_nos, jitter, jitter_dir, raw_noise, white_bkgd, eps, 0.0, clamp, layout, 8)
+        n, dev = keep[0].shape[0], keep[0].device
+        out = {k: torch.empty((n,) + self.MAPS[k], device=dev, dtype=f32) for k in want}
+        maps = _lib.TrainMaps(**{k: out[k].data_ptr() for k in want})
+        with torch.cuda.device(dev):
+            check(_lib.load().pnrf_train_stage2_fwd(self.handle, C.byref(bt), C.byref(maps), _stream()), 'pnrf_train_stage2_fwd')
+        self._split_n = n
+        return out
+
+    def backward(self, **cotangents):
+        """Backward half (pnrf_train_stage2_bwd) from the cotangents of the maps ``forward`` returned: keyword arguments named as the maps
+        (None / absent = zeros).  Leaves the 26 layers' gradients where ``fwd_bwd`` leaves them."""
+        n = getattr(self, '_split_n', None)
+        ptrs, keep = {}, []
+        for k, g in cotangents.items():
+            if k not in self.MAPS:
+                raise PnrfError(f'Trainer.backward: unknown map {k!r} (one of {list(self.MAPS)})')
+            if g is None:
+                continue
+            if not isinstance(g, torch.Tensor) or not g.is_cuda:
+                raise PnrfError(f'Trainer.backward: {k}: expected a GPU tensor (pronerf_amd has no CPU path)')
+            if n is not None and tuple(g.shape) != (n,) + self.MAPS[k]:
+                raise PnrfError(f'Trainer.backward: {k}: expected shape {(n,) + self.MAPS[k]}, got {tuple(g.shape)}')
+            g = g.detach().to(f32).contiguous()
+            keep.append(g)
+            ptrs['d_' + k] = g.data_ptr()
+        cot = _lib.TrainCotangents(**ptrs)
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_train_stage2_bwd(self.handle, C.byref(cot), _stream()), 'pnrf_train_stage2_bwd')
 
     def explore_fwd_bwd(self, rays, or_rays, target, img4, poses, K, ref_nos, n_mult, dir1, jitter, dir2, raw_noise=None, white_bkgd=False, eps=1e-6,
                         clamp=10.0, layout=1, want_rgb=True):

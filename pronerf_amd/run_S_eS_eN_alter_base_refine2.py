@@ -303,11 +303,16 @@ def config_parser():
     return _cp('refine2')
 
 
-def train(argv=None, device='cuda'):
+def train(argv=None, device='cuda', loss_fn=None):
     """Stage-2 training driver (run_S_eS_eN_alter_base_refine2.py:683-1000): LLFF scene, stage-1 checkpoint (--pretrain_path),
     pre-shuffled ray batches of all training views, one ``Trainer.fwd_bwd`` + ``adam_step`` per iteration with the reference's
     per-batch random draws and learning-rate decay, checkpoints with the reference's keys every ``i_weights``.
-    Returns (trainer, list of (iteration, loss, psnr))."""
+    Returns (trainer, list of (iteration, loss, psnr)).
+
+    loss_fn(maps, target, step) -> scalar tensor: train with that loss instead of the reference's — each iteration is then
+    ``autograd.render_train`` (``Trainer.forward``) -> loss_fn -> ``.backward()`` (``Trainer.backward``) -> ``adam_step``; ``maps`` holds
+    rgb_map1, rgb_map0, mm_rgb, depth, acc, disp, weights and z of the batch, the logged PSNR is still that of rgb_map1.  Without it the
+    loop is the fused ``fwd_bwd`` as before."""
     import os
     from .load_llff import load_llff_data
     from .render import N_SAMPLES
@@ -403,7 +408,15 @@ def train(argv=None, device='cuda'):
                              jitter_cap=1 - 2e-6, noise_cols=8 if args.raw_noise_std > 0 else 0, noise_std=args.raw_noise_std)
             head, jitter, noise = out[:7], out[7], (out[8] if args.raw_noise_std > 0 else None)
             jdir = 1 if random.random() > 0.5 else -1
-        loss, _ = tr.fwd_bwd(*head, jitter=jitter, jitter_dir=jdir, raw_noise=noise, white_bkgd=args.white_bkgd, a_mmrgb=args.a_mmrgb, want_rgb=False)
+        if loss_fn is None:
+            loss, _ = tr.fwd_bwd(*head, jitter=jitter, jitter_dir=jdir, raw_noise=noise, white_bkgd=args.white_bkgd, a_mmrgb=args.a_mmrgb, want_rgb=False)
+        else:
+            from .autograd import render_train
+            maps = render_train(tr, head[0], head[1], *head[3:], jitter=jitter, jitter_dir=jdir, raw_noise=noise, white_bkgd=args.white_bkgd)
+            total = loss_fn(maps, head[2], i)
+            total.backward()
+            with torch.no_grad():                        # [total, mse(rgb_map1)], as the fused call's loss[0:2]
+                loss = torch.stack([total.detach().reshape(()).float(), ((maps['rgb_map1'].detach() - head[2]) ** 2).mean()])
         if world > 1:
             from .dist import allreduce_gradients
             allreduce_gradients(tr)
