@@ -258,7 +258,13 @@ int pnrf_sampler_fwd(const pnrf_mlp_t* h, const float* rays, int64_t n, float* d
  * kappa < 0 selects PNRF_SAMPLER_KAPPA; kappa = 0 leaves only the fp32 round-off allowance (tests); NaN and values >= 1e30 are refused.
  * workspace: dev, 16-byte aligned, >= pnrf_sampler_workspace_bytes(n) bytes, contents irrelevant (its counters are reset on the stream
  * by every call); concurrent calls need separate workspaces.  Handles set to SAMPLER_SPLIT run the split kernel for every ray + pass 3;
- * SAMPLER_F32* handles run their single kernel. */
+ * SAMPLER_F32* handles run their single kernel.
+ * After the call (in stream order) the workspace stays readable as int32 words until the next call on it: word 1 = rays of pass 2, word 5 = rays of
+ * pass 3, words 16 .. 16 + [1] the list of pass 2 and words 16 + n .. 16 + n + [5] the list of pass 3 (ray numbers, distinct, in no particular order;
+ * what lies behind the counts is left over from earlier calls).
+ * Pinned by tests/test_twopass_flags_gpu.py against tests/twopass_ref.py: the critical kappa of every ray (the bound s with the kernel's constants,
+ * DESIGN.md 4.1) to a relative 1.4e-4, the flag's monotony in kappa, the rays flagged at every kappa (gap inside the allowance, not finite, fp16 limit),
+ * the lists, and bit for bit which kernel every output row comes from (n = 1 .. 257, past the grid cap, saturated rays, a second call on the same workspace). */
 #define PNRF_SAMPLER_KAPPA 2.0f
 int64_t pnrf_sampler_workspace_bytes(int64_t n);
 int pnrf_sampler_fwd_ws(const pnrf_mlp_t* h, const float* rays, int64_t n, float* depth_sorted, float* add_sorted,

@@ -343,10 +343,12 @@ def composite(raw, z, rays_d, add=None, mul=None, noise=None, clamp=0.0, white_b
     return rgb, disp, acc, w, depth
 
 
-def sampler_fwd(mlp: PackedMLP, rays, want_idx=True, want_rgb=True, want_raw=False, two_pass=False, kappa=None):
+def sampler_fwd(mlp: PackedMLP, rays, want_idx=True, want_rgb=True, want_raw=False, two_pass=False, kappa=None, want_lists=False, workspace=None):
     """pnrf_sampler_fwd; two_pass=True: pnrf_sampler_fwd_ws (plain-fp16 pass for every ray + split-fp16 pass for the undecided ones, what
     the fused path runs) and the numbers of rays of the second (split fp16) and third (exact fp32: saturated activations) pass as a seventh
-    and eighth return value (0-d int32 tensors on the device)."""
+    and eighth return value (0-d int32 tensors on the device).  want_lists=True: also the two lists themselves, as views [n] of the workspace
+    (int32 ray numbers in no particular order; only the first ``count`` entries of each belong to this call).  workspace: an int32 tensor of
+    at least pnrf_sampler_workspace_bytes(n) / 4 words to run on (a fresh one otherwise)."""
     rays = _chk(rays, 'rays', (11,))
     n, dev = rays.shape[0], rays.device
     depth = torch.empty(n, 8, device=dev, dtype=f32); add = torch.empty_like(depth); mul = torch.empty_like(depth)
@@ -356,9 +358,13 @@ def sampler_fwd(mlp: PackedMLP, rays, want_idx=True, want_rgb=True, want_raw=Fal
     if two_pass:
         lib = _lib.load()
         nb = int(lib.pnrf_sampler_workspace_bytes(n))
-        ws = torch.empty(max(nb, 64) // 4, device=dev, dtype=torch.int32)
+        ws = torch.empty(max(nb, 64) // 4, device=dev, dtype=torch.int32) if workspace is None else workspace
+        if ws.dtype != torch.int32 or ws.device != dev or not ws.is_contiguous() or ws.numel() * 4 < nb:
+            raise PnrfError(f'sampler_fwd: workspace must be a contiguous int32 tensor of at least {nb // 4} words on {dev}')
         check(lib.pnrf_sampler_fwd_ws(mlp.handle, _ptr(rays), n, _ptr(depth), _ptr(add), _ptr(mul), _ptr(idx), _ptr(rgb), _ptr(draw), _ptr(ws), nb,
                                       -1.0 if kappa is None else float(kappa), _stream()), 'pnrf_sampler_fwd_ws')
+        if want_lists:
+            return depth, idx, add, mul, rgb, draw, ws[1], ws[5], ws[16:16 + n], ws[16 + n:16 + 2 * n]
         return depth, idx, add, mul, rgb, draw, ws[1], ws[5]
     check(_lib.load().pnrf_sampler_fwd(mlp.handle, _ptr(rays), n, _ptr(depth), _ptr(add), _ptr(mul), _ptr(idx), _ptr(rgb), _ptr(draw), _stream()),
           'pnrf_sampler_fwd')

@@ -380,10 +380,15 @@ def test_two_pass_sampler_arguments(dev):
     assert call(p(ws), need, -1.0) == 0
     for k in (1, 255, 257):
         r = rays[:k].contiguous()
-        two = ops.sampler_fwd(mlps['sampler'], r, two_pass=True, want_raw=True)
+        two = ops.sampler_fwd(mlps['sampler'], r, two_pass=True, want_raw=True, want_lists=True)
         one = ops.sampler_fwd(mlps['sampler'], r, want_raw=True)
         assert torch.equal(two[1], one[1])                                                         # indices (no ties on these weights)
         np.testing.assert_allclose(two[0].cpu().numpy(), one[0].cpu().numpy(), rtol=0, atol=2e-3)
+        # ... exactly: a row on pass 2's list is the split kernel's, every other row the no-margin call's (tests/test_twopass_flags_gpu.py has the sizes between)
+        on = torch.zeros(k, dtype=torch.bool, device=dev)
+        on[two[8][:int(two[6])].long()] = True
+        p1 = ops.sampler_fwd(mlps['sampler'], r, two_pass=True, want_raw=True, kappa=0.0)
+        assert all(torch.equal(x[on], y[on]) and torch.equal(x[~on], z[~on]) for x, y, z in zip(two[:6], one[:6], p1[:6]))
         assert 0 <= int(two[6]) <= k and int(two[7]) == 0                                          # nothing saturates on these weights
     split = ops.PackedMLP(ops.NET_SAMPLER, w['sampler']['W'], w['sampler']['b'], variant='sampler_split')
     s2 = ops.sampler_fwd(split, rays, two_pass=True, want_raw=True)                                # variant handles run their one kernel

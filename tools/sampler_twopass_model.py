@@ -12,6 +12,11 @@ A ray is flagged when some adjacent sorted gap  g_i < KAPPA * (s_i + s_{i+1}).  
 wrong, and how many of those are NOT flagged (must be 0); max |error| / s over all samples (how conservative the model is).
 
     python tools/sampler_twopass_model.py [--rays 65536] [--kappa 6]
+
+This is a study of the MODEL, not a restatement of the kernel.  It differs from sampler_p1_kernel in three places: M_k per depth row where the kernel
+takes the max over the eight rows; S_l from the fp16-ROUNDED activations where the kernel squares them unrounded; true scale where the kernel's
+activations and constants carry log2(e) (p1c[0] = M / log2(e)^2), so every fp16 rounding falls differently (s moves by up to 1.7e-4).  The kernel's own
+decision, constant for constant, is tests/twopass_ref.py; tests/test_twopass_flags_cpu.py holds the two together.
 """
 import argparse
 import os
