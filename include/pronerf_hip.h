@@ -90,6 +90,11 @@ int pnrf_mlp_free(pnrf_mlp_t* h);
 int pnrf_mlp_serialize(const pnrf_mlp_t* h, void* buf, int64_t capacity, int64_t* size);
 int pnrf_mlp_deserialize(const void* buf, int64_t size, pnrf_mlp_t** out);
 int pnrf_mlp_kind(const pnrf_mlp_t* h, int* net, int* in_dim, int* in_dim_x, int* out_dim);
+/* The packer's host half: the engine image of a net, written to HOST memory without touching a device — byte for byte what
+ * pnrf_mlp_serialize(pnrf_mlp_pack(...)) writes.  Arguments, checks, return codes and messages as pnrf_mlp_pack; (buf, capacity, size) as
+ * pnrf_mlp_serialize (buf == NULL only reports the size).  pnrf_mlp_pack itself is this followed by the upload pnrf_mlp_deserialize makes. */
+int pnrf_mlp_pack_image(int net, const float* const* W, const float* const* b, const int* in_dim,
+                        const int* out_dim, int n_layers, void* buf, int64_t capacity, int64_t* size);
 int pnrf_mlp_skips(const pnrf_mlp_t* h, uint32_t* mask);
 
 /* Kernel variant of a packed network.  PNRF_VARIANT_DEFAULT is what pack / deserialize produce and what every product path runs:

@@ -31,6 +31,7 @@ SIGNATURES = {
     'pnrf_abi_version': (_i, []),
     'pnrf_last_error': (C.c_char_p, []),
     'pnrf_mlp_pack': (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_p)]),
+    'pnrf_mlp_pack_image': (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p, _i64, C.POINTER(_i64)]),
     'pnrf_mlp_free': (_i, [_p]),
     'pnrf_mlp_serialize': (_i, [_p, _p, _i64, C.POINTER(_i64)]),
     'pnrf_mlp_deserialize': (_i, [_p, _i64, C.POINTER(_p)]),

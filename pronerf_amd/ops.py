@@ -50,15 +50,9 @@ class PackedMLP:
         """variant: None / 'default', or one of ``_lib.VARIANTS`` ('sampler_f32', 'sampler_f32_full', 'bf16_32x32') — fixed for the
         life of the handle (pnrf_mlp_set_variant); nothing is read from the environment."""
         lib = _lib.load()
-        n = len(weights)
-        ws = [np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float32) for b in biases]
-        Wp = (C.c_void_p * n)(*[w.ctypes.data for w in ws])
-        bp = (C.c_void_p * n)(*[b.ctypes.data for b in bs])
-        ind = (C.c_int * n)(*[w.shape[1] for w in ws])
-        outd = (C.c_int * n)(*[w.shape[0] for w in ws])
+        (ws, _bs), args = self._pack_args(weights, biases)
         h = C.c_void_p()
-        check(lib.pnrf_mlp_pack(net, Wp, bp, ind, outd, n, C.byref(h)), 'pnrf_mlp_pack')
+        check(lib.pnrf_mlp_pack(net, *args, C.byref(h)), 'pnrf_mlp_pack')
         self.handle = h
         self.net = net
         self.in_dim = ws[0].shape[1]
@@ -67,6 +61,27 @@ class PackedMLP:
         self.variant = 'default'
         if variant not in (None, 'default'):
             self.set_variant(variant)
+
+    @staticmethod
+    def _pack_args(weights, biases):
+        """-> ((float32 weight arrays, bias arrays): to be kept alive over the call, (W, b, in_dim, out_dim, n_layers) of pnrf_mlp_pack / pnrf_mlp_pack_image)."""
+        n = len(weights)
+        ws = [np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32) for w in weights]
+        bs = [np.ascontiguousarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float32) for b in biases]
+        Wp = (C.c_void_p * n)(*[w.ctypes.data for w in ws])
+        bp = (C.c_void_p * n)(*[b.ctypes.data for b in bs])
+        return (ws, bs), (Wp, bp, (C.c_int * n)(*[w.shape[1] for w in ws]), (C.c_int * n)(*[w.shape[0] for w in ws]), n)
+
+    @classmethod
+    def pack_image(cls, net: int, weights, biases) -> bytes:
+        """The engine image of a net packed on the host (pnrf_mlp_pack_image): the bytes ``PackedMLP(net, weights, biases).serialize()`` returns, without a device."""
+        lib = _lib.load()
+        _keep, args = cls._pack_args(weights, biases)
+        size = C.c_int64()
+        check(lib.pnrf_mlp_pack_image(net, *args, None, 0, C.byref(size)), 'pnrf_mlp_pack_image')
+        buf = (C.c_char * size.value)()
+        check(lib.pnrf_mlp_pack_image(net, *args, buf, size.value, C.byref(size)), 'pnrf_mlp_pack_image')
+        return bytes(buf)
 
     def set_variant(self, variant):
         """Configuration step (before the handle is used by a context / stream)."""

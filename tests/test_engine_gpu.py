@@ -56,6 +56,20 @@ def test_engine_round_trip_is_bit_exact(dev, kind):
             ops.PackedMLP.deserialize(blob, expect_net=(a.net + 1) % 4)
 
 
+def test_host_packed_image_is_the_serialized_handle(dev):
+    """pnrf_mlp_pack_image (host only) writes the bytes pack -> serialize reads back from the device, and an image loaded from those bytes serializes to
+    them again: Fern sampler and refine net, a refine net with skip connections, DoNeRFTRT and the NeRF class."""
+    from pronerf_amd import ops
+    w, wskip = synth.make_weights(3, 'trained'), synth.make_weights(3, 'trained', mmnetskips=[4])
+    cls = _cls_stack(synth.make_nerfcls_weights(3))
+    nets = [(ops.NET_SAMPLER, w['sampler']), (ops.NET_REFINE, w['refine']), (ops.NET_REFINE, wskip['refine']), (ops.NET_NERF, w['nerf']), (ops.NET_NERFCLS, cls)]
+    with torch.cuda.device(dev):
+        for net, x in nets:
+            image = ops.PackedMLP.pack_image(net, x['W'], x['b'])
+            assert ops.PackedMLP(net, x['W'], x['b']).serialize() == image
+            assert ops.PackedMLP.deserialize(image, expect_net=net).serialize() == image
+
+
 def test_damaged_and_foreign_engines_are_refused(dev):
     from pronerf_amd import ops
     with torch.cuda.device(dev):
