@@ -576,6 +576,28 @@ int64_t pnrf_image_metrics_workspace_bytes(int H, int W, int T);
 int pnrf_image_metrics_fwd(const float* pred, int pred_stride, const float* gt, int gt_stride, int H, int W,
                            const float* taps, int T, float max_val, float k1, float k2, double* out,
                            float* ssim_map, void* workspace, int64_t workspace_bytes, void* stream);
+/* img2ssim as a training loss: the mean SSIM of B patch pairs of H x W x 3 and its gradient with respect to the prediction, in two launches.
+ * pred, gt: dev fp32, patch b pixel (y, x) channel c at [b patch_stride + (y W + x) stride + c]: a pixel stride in floats (>= 3) per operand as
+ * above, and a patch stride in floats (>= 0; 0 reads one patch B times) per operand.  taps: HOST [T], 1 <= T <= 16, H >= T, W >= T;
+ * 1 <= B <= 21845 (a patch and channel per grid z).  The forward arithmetic is that of pnrf_image_metrics_fwd, one kernel text for both: for
+ * B = 1 the mean has the bits of that call's out[3].
+ * out: dev double[2] = {sum of the SSIM map over all B (H-T+1) (W-T+1) 3 values, its mean}.  d_pred: dev fp32 [B,H,W,3], dense =
+ * d mean / d pred.  The loss 1 - mean, its weight and the sign are the caller's.
+ * Gradient: with x' = pred - max_val / 2, y' = gt - max_val / 2 and the window's filter weights w, every window and channel gives
+ * w_p (a + 2 b x'_p + e y'_p) to its pixel p:  b = dS/ds00 through the clamp (zero unless s00 > 0);  e = dS/ds01 through the limiter (dS/dc
+ * where |s01| <= sqrt(v0 v1); otherwise 0, and b gains sign(s01) 1/2 sqrt(v1 / v0) dS/dc where v0 > 0);  a = dS/dmu0 (direct) - 2 m0 b - m1 e
+ * with the means m0, m1 of x', y'.  The first pass (the metrics kernel's tiling) writes a, b, e per window into the workspace; the second is
+ * the transposed separable convolution of the three planes as a gather per pixel, 32 x 32 pixels per workgroup, patch and channel:
+ * d_pred[p] = (F^T[a] + 2 x'_p F^T[b] + y'_p F^T[e]) / (B (H-T+1) (W-T+1) 3); its first workgroup adds the fp64 partial sums in a fixed order.
+ * No atomics: value and gradient are bit-identical from call to call on any stream.
+ * Deviation from autograd, exactly ON a kink only: torch.maximum / minimum split the gradient between equal operands; here s00 == 0 takes
+ * b = 0 and |s01| == sqrt(v0 v1) counts as the limiter being inactive.  A NaN reaches the windows, and the pixels, that contain it — no others.
+ * workspace: dev, 8-byte aligned, >= pnrf_ssim_loss_workspace_bytes(B, H, W, T) bytes (0 for sizes the call refuses), contents irrelevant;
+ * concurrent calls need separate workspaces.  Everything outside the limits above returns PNRF_E_ARG before any launch. */
+int64_t pnrf_ssim_loss_workspace_bytes(int B, int H, int W, int T);
+int pnrf_ssim_loss_fwd(const float* pred, int pred_stride, int64_t pred_patch_stride, const float* gt, int gt_stride,
+                       int64_t gt_patch_stride, int B, int H, int W, const float* taps, int T, float max_val, float k1,
+                       float k2, double* out, float* d_pred, void* workspace, int64_t workspace_bytes, void* stream);
 /* to8b of a frame (run_nerf_helpers.py:135; run_S_eS_eN_alter_trt.py:356, 360): rgb8[n,3] = to8b(rgb), depth8[n] = to8b(depth / max(depth)),
  * uint8, bit-identical to numpy for finite input — 255 * clip(x, 0, 1) is one fp32 product, truncated; the quotient is one correctly
  * rounded fp32 division by the maximum, which a first kernel takes on the device.  rgb: dev, pixel i at [i rgb_stride + c], rgb_stride >= 3;

@@ -76,6 +76,8 @@ SIGNATURES = {
     # frame tail: image metrics and 8-bit output
     'pnrf_image_metrics_workspace_bytes': (_i64, [_i, _i, _i]),
     'pnrf_image_metrics_fwd': (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _p, _p, _p, _i64, _p]),
+    'pnrf_ssim_loss_workspace_bytes': (_i64, [_i, _i, _i, _i]),
+    'pnrf_ssim_loss_fwd': (_i, [_p, _i, _i64, _p, _i, _i64, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _p, _p, _p, _i64, _p]),
     'pnrf_frame_to8b_fwd': (_i, [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p]),
     # device-resident scene: pose -> frame
     'pnrf_scene_create': (_i, [_i, _i, _i, _i, C.POINTER(_p)]),

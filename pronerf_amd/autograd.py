@@ -13,6 +13,9 @@ gradient.  No arithmetic happens here: a cotangent is made a contiguous float32 
 One forward is good for one backward (the activations are the trainer's own buffers): a second backward through the same graph, or one
 after any other trainer call, raises ``PnrfError`` with the library's PNRF_E_STATE message.  No second-order gradients, and none with
 respect to rays or images.
+
+``ssim`` is the mean img2ssim of image patches as a differentiable scalar (``ops.ssim_loss``: value and gradient from one kernel pair), for
+a structural term in such a loss when the batch is made of patches (the stage-2 driver's ``patch_size``).
 """
 from __future__ import annotations
 
@@ -43,6 +46,27 @@ class _RenderTrain(torch.autograd.Function):
             raise PnrfError('render_train: backward without a cotangent for any map')
         ctx.trainer.backward(**cot)
         return None, None, None, None, None              # nothing flows to the anchor or the data; the gradients are in the trainer
+
+
+class _Ssim(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, kwargs):
+        from . import ops
+        mean, d_pred = ops.ssim_loss(pred, gt, **kwargs)
+        ctx.save_for_backward(d_pred)                    # the kernel pair leaves the gradient with the value: backward has nothing to launch but a product
+        return mean.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad):
+        d_pred, = ctx.saved_tensors
+        return grad * d_pred, None, None                 # no gradient with respect to gt
+
+
+def ssim(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03):
+    """Mean SSIM of [B,H,W,3] or [H,W,3] patches (``ops.ssim_loss``) as a float32 scalar, differentiable with respect to ``pred`` — for a loss
+    such as ``mse + lam * (1 - ssim(pred, gt))``.  The gradient is computed with the value and kept; backward is one multiply by the incoming
+    gradient, without a host sync.  ``gt`` gets none; no second-order gradients."""
+    return _Ssim.apply(pred, gt, dict(max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2))
 
 
 def render_train(trainer, rays, or_rays, img4, poses, K, ref_nos, jitter=None, jitter_dir=1, raw_noise=None, white_bkgd=False, eps=1e-5, clamp=0.0,

@@ -762,6 +762,74 @@ def image_metrics(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.
     return (out, smap) if return_map else out
 
 
+def _patches(t, name):
+    """[B,H,W,3] patches whose pixels hold 3 contiguous floats, lie a constant number of floats apart inside a patch (rows without gaps) and
+    whose patches lie any number of floats apart, as (tensor, pixel stride, patch stride) without a copy; any other layout is made contiguous."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PnrfError(f'{name}: expected a GPU tensor (pronerf_amd has no CPU path)')
+    if t.dtype != f32:
+        raise PnrfError(f'{name}: expected float32, got {t.dtype}')
+    B, H, W, _ = t.shape
+    sb, sy, sx, sc = t.stride()
+    if sc == 1 and sx >= 3 and (H == 1 or sy == W * sx) and (B == 1 or sb >= 0):
+        return t, int(sx), int(sb) if B > 1 else 0
+    return t.contiguous(), 3, H * W * 3
+
+
+_ssim_workspaces = {}      # (device index, stream, B, H, W, T) -> workspace: calls on one stream follow each other, so they may share one
+
+
+def ssim_loss(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03):
+    """The mean SSIM of B patch pairs and its gradient with respect to ``pred`` (pnrf_ssim_loss_fwd; the arithmetic of ``image_metrics``).
+    ``pred`` / ``gt``: [B,H,W,3] or [H,W,3]; views with a pixel stride above 3 and any patch stride are read in place.  Returns (mean SSIM as a
+    0-d float64 device tensor, d mean / d pred as a float32 tensor shaped like ``pred``) — nothing is read back.  The loss 1 - mean and its
+    weight are the caller's (``autograd.ssim`` makes it differentiable)."""
+    lib = _lib.load()
+    if pred.dim() not in (3, 4) or pred.shape[-1] != 3 or pred.shape != gt.shape:
+        raise PnrfError(f'ssim_loss: expected two [B,H,W,3] or [H,W,3] tensors of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}')
+    shape = tuple(pred.shape)
+    B, H, W = (1,) * (pred.dim() == 3) + tuple(int(x) for x in shape[:-1])
+    T = int(filter_size)
+    if not 1 <= T <= 16 or H < T or W < T:
+        raise PnrfError(f'ssim_loss: filter_size {T} must be 1 .. 16 and fit the {H} x {W} patches')
+    if not 1 <= B <= 21845:
+        raise PnrfError(f'ssim_loss: {B} patches, one call takes 1 .. 21845')
+    pred, sp, pp = _patches(pred.reshape(B, H, W, 3) if pred.dim() == 3 else pred, 'pred')
+    gt, sg, pg = _patches(gt.reshape(B, H, W, 3) if gt.dim() == 3 else gt, 'gt')
+    if gt.device != pred.device:
+        raise PnrfError('ssim_loss: pred and gt are on different devices')
+    taps = np.ascontiguousarray(ssim_filter(T, filter_sigma), dtype=np.float32)
+    with torch.cuda.device(pred.device):
+        nb = int(lib.pnrf_ssim_loss_workspace_bytes(B, H, W, T))
+        key = (pred.device.index, torch.cuda.current_stream().cuda_stream, B, H, W, T)
+        ws = _ssim_workspaces.get(key)
+        if ws is None:
+            if len(_ssim_workspaces) >= 64:
+                _ssim_workspaces.clear()
+            ws = _ssim_workspaces[key] = torch.empty((nb + 7) // 8, device=pred.device, dtype=torch.float64)
+        out = torch.empty(2, device=pred.device, dtype=torch.float64)
+        d_pred = torch.empty(shape, device=pred.device, dtype=f32)
+        check(lib.pnrf_ssim_loss_fwd(_ptr(pred), sp, pp, _ptr(gt), sg, pg, B, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), T, float(max_val),
+                                     float(k1), float(k2), _ptr(out), _ptr(d_pred), _ptr(ws), nb, _stream()), 'pnrf_ssim_loss_fwd')
+    return out[1], d_pred
+
+
+def patch_indices(nv, H, W, patch, count, generator=None, device=None):
+    """Ray indices [count patch^2] (int64, on the device) of ``count`` ``patch`` x ``patch`` crops placed uniformly over the views and the
+    positions at which a crop lies inside its view: patch-major, row-major inside a patch, in ``TrainSet``'s numbering
+    g = view H W + y W + x.  Drawn by torch on the device (``generator``'s, else ``device``, else the current one): no host sync."""
+    nv, H, W, patch, count = int(nv), int(H), int(W), int(patch), int(count)
+    if nv < 1 or count < 1 or not 1 <= patch <= min(H, W):
+        raise PnrfError(f'patch_indices: need nv >= 1, count >= 1 and 1 <= patch <= min(H, W), got nv {nv}, count {count}, patch {patch} in {H} x {W}')
+    dev = generator.device if generator is not None else torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    ny, nx = H - patch + 1, W - patch + 1
+    place = torch.randint(nv * ny * nx, (count,), device=dev, generator=generator)          # one draw: view, row and column of the crop's corner
+    v, rest = place // (ny * nx), place % (ny * nx)
+    corner = v * (H * W) + (rest // nx) * W + rest % nx
+    k = torch.arange(patch, device=dev)
+    return (corner[:, None] + (k[:, None] * W + k[None, :]).reshape(1, -1)).reshape(-1)
+
+
 def frame_to8b(rgb=None, depth=None, rgbd=None):
     """to8b(rgb) and to8b(depth / max(depth)) as uint8 device tensors (pnrf_frame_to8b_fwd; helpers:135, trt.py:356-360), bit-identical to
     numpy for finite input (NaN -> 0).  ``rgbd`` [n,4] (the renderer's rows), or ``rgb`` [..., 3] and / or ``depth`` [...] — views into

@@ -303,7 +303,7 @@ def config_parser():
     return _cp('refine2')
 
 
-def train(argv=None, device='cuda', loss_fn=None):
+def train(argv=None, device='cuda', loss_fn=None, patch_size=0):
     """Stage-2 training driver (run_S_eS_eN_alter_base_refine2.py:683-1000): LLFF scene, stage-1 checkpoint (--pretrain_path),
     pre-shuffled ray batches of all training views, one ``Trainer.fwd_bwd`` + ``adam_step`` per iteration with the reference's
     per-batch random draws and learning-rate decay, checkpoints with the reference's keys every ``i_weights``.
@@ -312,7 +312,11 @@ def train(argv=None, device='cuda', loss_fn=None):
     loss_fn(maps, target, step) -> scalar tensor: train with that loss instead of the reference's — each iteration is then
     ``autograd.render_train`` (``Trainer.forward``) -> loss_fn -> ``.backward()`` (``Trainer.backward``) -> ``adam_step``; ``maps`` holds
     rgb_map1, rgb_map0, mm_rgb, depth, acc, disp, weights and z of the batch, the logged PSNR is still that of rgb_map1.  Without it the
-    loop is the fused ``fwd_bwd`` as before."""
+    loop is the fused ``fwd_bwd`` as before.
+
+    patch_size > 0: every batch is N_rand // patch_size^2 crops of patch_size x patch_size pixels (``ops.patch_indices``) instead of a slice
+    of the pixel permutation, for a loss that needs image structure (``autograd.ssim``): the rows of ``maps`` and ``target`` then reshape to
+    [count, patch_size, patch_size, .].  Needs --device_batches rays|all, a single replica and N_rand divisible by patch_size^2."""
     import os
     from .load_llff import load_llff_data
     from .render import N_SAMPLES
@@ -332,6 +336,10 @@ def train(argv=None, device='cuda', loss_fn=None):
     if args.N_rand % world:
         raise ValueError(f'N_rand = {args.N_rand} is not divisible by the {world} replicas')
     n_local = args.N_rand // world
+    patch_size = int(patch_size)
+    if patch_size < 0 or (patch_size and (args.device_batches == 'off' or world > 1 or args.N_rand % patch_size ** 2)):
+        raise PnrfError(f'patch_size = {patch_size} needs --device_batches rays|all (got {args.device_batches}), a single replica (got {world}) and '
+                        f'N_rand divisible by patch_size^2 (N_rand = {args.N_rand})')
     images, poses, bds, _, i_test = load_llff_data(args.datadir, args.factor, recenter=True, bd_factor=.75, spherify=args.spherify)
     hwf = poses[0, :3, -1]
     poses = poses[:, :3, :4]
@@ -381,15 +389,20 @@ def train(argv=None, device='cuda', loss_fn=None):
     # resumed runs continue on the decayed schedule (the reference restores it through optimizer.load_state_dict, :402-412)
     lr = args.lrate * (0.1 ** (start / (args.lrate_decay * 1000)))
     nv = len(i_train)
+    if patch_size > min(H, W):
+        raise PnrfError(f'patch_size = {patch_size} does not fit the {H} x {W} training views')
     for i in range(start + 1, n_iters):
-        idx = perm[i_batch:i_batch + args.N_rand]
-        i_batch += args.N_rand
-        if i_batch >= n_total:                                                                                  # :840-844
-            epoch += 1
-            perm = shared_permutation(n_total, epoch, dev) if world > 1 else torch.randperm(n_total, device=dev); i_batch = 0
-        if idx.shape[0] < args.N_rand:
-            continue
-        idx = idx[replica * n_local:(replica + 1) * n_local]                                                          # this replica's share
+        if patch_size:                                   # crops instead of the permutation's pixels: the batch's rows are patch-major, row-major inside
+            idx = ops.patch_indices(nv, H, W, patch_size, args.N_rand // patch_size ** 2, device=dev)
+        else:
+            idx = perm[i_batch:i_batch + args.N_rand]
+            i_batch += args.N_rand
+            if i_batch >= n_total:                                                                              # :840-844
+                epoch += 1
+                perm = shared_permutation(n_total, epoch, dev) if world > 1 else torch.randperm(n_total, device=dev); i_batch = 0
+            if idx.shape[0] < args.N_rand:
+                continue
+            idx = idx[replica * n_local:(replica + 1) * n_local]                                                      # this replica's share
         # the per-batch draws of render_rays (:594-600, :649-661, raw2outputs :497)
         if mode == 'off':
             order = torch.as_tensor(sorted(random.sample(range(nv - 1), 4)), device=dev)

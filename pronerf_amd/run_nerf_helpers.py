@@ -12,6 +12,7 @@ Same names, argument meaning and error behaviour as the live subset of the refer
     NeRF                           helpers:792-847   -> pnrf_mlp_fwd (bf16 MFMA, skip + view branch)
     get_rays / ndc_rays            helpers:2705-2714, 2776-2793 -> pnrf_frame_rays_fwd / pnrf_ndc_rays_fwd
     img2ssim                       helpers:151-197   -> pnrf_image_metrics_fwd
+    img2ssim gradient              (autograd of :151-197) -> pnrf_ssim_loss_fwd  (ops.ssim_loss, autograd.ssim)
 
 The model classes keep the reference's ``state_dict`` keys (``fc_backbone.{i}.*``, ``fc_output.*``,
 ``layers.{i}.*``) so checkpoints interchange; their parameters are re-packed into the device weight
