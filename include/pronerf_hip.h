@@ -608,6 +608,52 @@ int pnrf_ssim_loss_fwd(const float* pred, int pred_stride, int64_t pred_patch_st
 int pnrf_frame_to8b_fwd(const float* rgb, int rgb_stride, const float* depth, int depth_stride, int64_t n,
                         uint8_t* rgb8, uint8_t* depth8, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- LPIPS (version 0.1) of an image pair: AlexNet / VGG-16 feature stacks and the metric ---------------------
+ * The third number the method is reported with (run_nerf_helpers.py:137-149: rgb_lpips, nets 'alex' and 'vgg').  The weights are the caller's:
+ * the backbone's convolutions and the five 1 x 1 'lin' layers; nothing is fetched from anywhere.
+ * Definition.  Two H x W x 3 images a, b; with normalize x <- 2 x - 1; then (x - shift) / scale per channel, shift = (-.030, -.088, -.188),
+ * scale = (.458, .448, .450).  Five taps F_k (ReLU outputs):
+ *   alex: conv(3->64, k 11, stride 4, pad 2) | maxpool(3, 2) conv(64->192, k 5, pad 2) | maxpool(3, 2) conv(192->384, k 3, pad 1) |
+ *         conv(384->256, k 3, pad 1) | conv(256->256, k 3, pad 1), a tap behind each;
+ *   vgg:  thirteen conv(k 3, pad 1) of widths 64 64 | 128 128 | 256 256 256 | 512 512 512 | 512 512 512, maxpool(2, 2) between the groups, a
+ *         tap behind the last layer of each group.
+ * Pooling has no padding and floor sizes.  Per tap and pixel n(F) = F / (sqrt(sum_c F_c^2) + 1e-10),
+ * m_k[y,x] = sum_c lin_k[c] (n(F_k(a)) - n(F_k(b)))_c^2, and d = sum_k mean_yx m_k.  Sides: alex 31 .. PNRF_LPIPS_MAX_DIM (the second pool needs a
+ * 3 x 3 input), vgg 16 .. PNRF_LPIPS_MAX_DIM.
+ * Arithmetic: every convolution is an implicit GEMM on the exact-fp32 MFMA (fp32 products and range, sums in (ky, kx, c_in) order), the pair as a
+ * batch of two; the tap sums are fp32 per pixel and fp64 over pixels, per-workgroup partial sums added in a fixed order by a last small kernel:
+ * no atomics, results bit-identical from call to call on any stream; d(x, x) is exactly 0 and d(a, b) has the bits of d(b, a).
+ *
+ * pnrf_lpips_create: net "alex" or "vgg" (anything else: PNRF_E_ARG).  conv_w[n_conv], conv_b[n_conv]: pointers to fp32 [out,in,kh,kw] / [out]
+ * (torch layout), on the host or on a device; conv_shape: HOST int[n_conv][4] = the shapes of conv_w; lin_w[5]: pointers to fp32 [C_k];
+ * lin_dim: HOST int[5].  Every shape is checked against the net's table before any device work (PNRF_E_SHAPE; the message lists the table).  The
+ * weights are repacked once, [K][C_out], on the current device. */
+#define PNRF_LPIPS_MAX_DIM 4096
+typedef struct pnrf_lpips pnrf_lpips_t;
+int pnrf_lpips_create(const char* net, const float* const* conv_w, const float* const* conv_b, const int* conv_shape, int n_conv,
+                      const float* const* lin_w, const int* lin_dim, pnrf_lpips_t** out);
+int pnrf_lpips_free(pnrf_lpips_t* h);
+/* Host only: hw = HOST int[5][2], the rows and columns of the five tap planes of an H x W image.  PNRF_E_ARG for an unknown net or a side outside
+ * the limits above. */
+int pnrf_lpips_tap_dims(const char* net, int H, int W, int* hw);
+/* Bytes of workspace pnrf_lpips_fwd needs at H x W: two activation buffers and the partial sums.  0 for sizes the call refuses. */
+int64_t pnrf_lpips_workspace_bytes(const pnrf_lpips_t* h, int H, int W);
+/* a, b: dev fp32, pixel (y, x) channel c at [(y W + x) stride + c], pixel strides in floats >= 3 as pnrf_image_metrics_fwd (4 reads rgbd rows in
+ * place).  out: dev double[6] = {d, mean m_1 .. mean m_5}.  maps: dev fp32, the five m_k planes concatenated (sizes: pnrf_lpips_tap_dims), or NULL.
+ * workspace: dev, 16-byte aligned, >= pnrf_lpips_workspace_bytes(h, H, W) bytes, contents irrelevant; concurrent calls need separate workspaces.
+ * Nothing is allocated and nothing is read back: the call is capturable in a hipGraph.  A null pointer, a stride below 3 or a size outside the
+ * limits return PNRF_E_ARG before any launch. */
+int pnrf_lpips_fwd(const pnrf_lpips_t* h, const float* a, int a_stride, const float* b, int b_stride, int H, int W, int normalize,
+                   double* out, float* maps, void* workspace, int64_t workspace_bytes, void* stream);
+/* For tests: conv layer `layer` of the handle — with pool_first its preceding max pooling, then conv, bias, ReLU — on a dense NHWC pair
+ * x: dev fp32 [2,H,W,C_in] -> y: dev fp32 [2,OH,OW,C_out], with the very kernels pnrf_lpips_fwd runs (layer 0: its gather without the input
+ * scaling).  pool_first on a layer without a pooling in front, an input smaller than the window / filter, x (hidden layers) or y not 16-byte
+ * aligned: PNRF_E_ARG.  workspace: >= pnrf_lpips_layer_workspace_bytes bytes (layer 0: the gathered rows; pool_first: the pooled pair; else 0
+ * and the pointer may be NULL). */
+int64_t pnrf_lpips_layer_workspace_bytes(const pnrf_lpips_t* h, int layer, int pool_first, int H, int W);
+int pnrf_lpips_layer_fwd(const pnrf_lpips_t* h, int layer, int pool_first, const float* x, int H, int W, float* y, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
 /* ---- device-resident scene: a frame from a camera pose alone ---------------------------------------
  * What render_path does per pose on the host (run_S_eS_eN_alter_trt.py:245-302: rank the source cameras, fetch / permute / upload the neighbour
  * images, build the projection matrices, build the rays) from a scene that lives on the device.  The source views are fixed, so they are uploaded

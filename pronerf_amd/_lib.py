@@ -79,6 +79,14 @@ SIGNATURES = {
     'pnrf_ssim_loss_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'pnrf_ssim_loss_fwd': (_i, [_p, _i, _i64, _p, _i, _i64, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _p, _p, _p, _i64, _p]),
     'pnrf_frame_to8b_fwd': (_i, [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p]),
+    # LPIPS: feature stacks and the metric
+    'pnrf_lpips_create': (_i, [C.c_char_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p)]),
+    'pnrf_lpips_free': (_i, [_p]),
+    'pnrf_lpips_tap_dims': (_i, [C.c_char_p, _i, _i, C.POINTER(_i)]),
+    'pnrf_lpips_workspace_bytes': (_i64, [_p, _i, _i]),
+    'pnrf_lpips_fwd': (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
+    'pnrf_lpips_layer_workspace_bytes': (_i64, [_p, _i, _i, _i, _i]),
+    'pnrf_lpips_layer_fwd': (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _i64, _p]),
     # device-resident scene: pose -> frame
     'pnrf_scene_create': (_i, [_i, _i, _i, _i, C.POINTER(_p)]),
     'pnrf_scene_free': (_i, [_p]),

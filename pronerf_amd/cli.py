@@ -60,6 +60,9 @@ def infer_argv(ns):
         argv += ['--max_images', str(ns.max_images)]
     if getattr(ns, 'metrics', None) is not None:
         argv += ['--metrics', ns.metrics]
+    for k in ('lpips_net', 'lpips_backbone', 'lpips_lin'):
+        if getattr(ns, k, None) is not None:
+            argv += ['--' + k, getattr(ns, k)]
     if getattr(ns, 'device_to8b', False):
         argv.append('--device_to8b')
     if getattr(ns, 'scene_cache', None) is not None:
@@ -113,7 +116,11 @@ def build_parser():
         q.add_argument('extra', nargs=argparse.REMAINDER, help='additional arguments for the underlying driver; prefix with --')
 
     def frame_tail(q):
-        q.add_argument('--metrics', choices=['psnr', 'psnr,ssim'], default=None, help="'psnr,ssim': PSNR and SSIM of the rendered test views, taken on the device")
+        q.add_argument('--metrics', choices=['psnr', 'psnr,ssim', 'psnr,ssim,lpips'], default=None,
+                       help="'psnr,ssim': PSNR and SSIM of the rendered test views, taken on the device; 'psnr,ssim,lpips': also LPIPS (needs --lpips_backbone and --lpips_lin)")
+        q.add_argument('--lpips_net', '--lpips-net', choices=['alex', 'vgg'], default=None, dest='lpips_net', help='backbone of LPIPS (default vgg)')
+        q.add_argument('--lpips_backbone', '--lpips-backbone', default=None, dest='lpips_backbone', help="the torchvision state dict of the backbone (a file the user brings)")
+        q.add_argument('--lpips_lin', '--lpips-lin', default=None, dest='lpips_lin', help="the lpips package's weights/v0.1/<net>.pth (a file the user brings)")
         q.add_argument('--device_to8b', '--device-to8b', action='store_true', dest='device_to8b', help='8-bit PNG planes converted on the device')
         q.add_argument('--scene_cache', '--scene-cache', choices=['f32', 'u8'], default=None, dest='scene_cache',
                        help="source views resident on the device, every pose rendered from its twelve floats ('u8': RGBA8 texels)")

@@ -814,6 +814,168 @@ def ssim_loss(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, 
     return out[1], d_pred
 
 
+# ------------------------------------------------------------------------------------------ LPIPS
+# torch shapes [out, in, kh, kw] of the backbones' conv layers and the channels of the five 'lin' layers (include/pronerf_hip.h)
+LPIPS_CONVS = {'alex': [(64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3)],
+               'vgg': [(64, 3, 3, 3), (64, 64, 3, 3), (128, 64, 3, 3), (128, 128, 3, 3), (256, 128, 3, 3), (256, 256, 3, 3), (256, 256, 3, 3),
+                       (512, 256, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3)]}
+LPIPS_LIN = {'alex': (64, 192, 384, 256, 256), 'vgg': (64, 128, 256, 512, 512)}
+LPIPS_MIN = {'alex': 31, 'vgg': 16}
+LPIPS_MAX_DIM = 4096
+
+
+def _lpips_state(sd, what):
+    """A state dict, or the path of one (loaded on the CPU, tensors only)."""
+    if isinstance(sd, (str, bytes)) or hasattr(sd, '__fspath__'):
+        sd = torch.load(sd, map_location='cpu', weights_only=True)
+    if not isinstance(sd, dict):
+        raise PnrfError(f'Lpips: {what} must be a state dict or the path of one, got {type(sd).__name__}')
+    return sd
+
+
+def lpips_weights(net, backbone, lin):
+    """(conv weights, conv biases, lin vectors) as contiguous fp32 CPU tensors from a backbone state dict — the 4-D ``….<idx>.weight`` / ``.bias``
+    entries in index order: torchvision's ``features.<idx>.*`` or the lpips package's ``net.slice<k>.<idx>.*`` — and a lin state dict — entries
+    named ``lin<k>…weight``, k = 0 .. 4 in order, [1,C,1,1] or [C].  Anything else raises a PnrfError that names the key and the expected shape."""
+    import re
+    if net not in LPIPS_CONVS:
+        raise PnrfError(f"Lpips: unknown net {net!r}; the kernels take 'alex' and 'vgg'")
+    backbone, lin = _lpips_state(backbone, 'backbone'), _lpips_state(lin, 'lin')
+    is_lin = re.compile(r'(^|\.)lin(\d+)(\.|$)')
+    any_lin = re.compile(r'(^|\.)lins?\d*(\.|$)')                 # lin<k>.* and the lpips module's lins.<k>.* list: 4-D, but no conv layers of the backbone
+    found = []
+    for k, v in backbone.items():
+        m = re.search(r'(^|\.)(\d+)\.weight$', k)
+        if m and isinstance(v, torch.Tensor) and v.dim() == 4 and not any_lin.search(k):
+            found.append((int(m.group(2)), k))
+    found.sort()
+    shapes = LPIPS_CONVS[net]
+    if len(found) != len(shapes):
+        raise PnrfError(f"Lpips: backbone of {net!r} needs {len(shapes)} conv layers ('<idx>.weight' of shapes {shapes}), found {len(found)}: "
+                        f'{[k for _, k in found]}')
+    W, B = [], []
+    for (_, k), shp in zip(found, shapes):
+        if tuple(backbone[k].shape) != shp:
+            raise PnrfError(f'Lpips: {k} has shape {tuple(backbone[k].shape)}, expected {shp}')
+        kb = k[:-len('weight')] + 'bias'
+        if kb not in backbone or tuple(backbone[kb].shape) != (shp[0],):
+            raise PnrfError(f'Lpips: {kb} is missing or not of shape {(shp[0],)}')
+        W.append(backbone[k].detach().to('cpu', f32).contiguous())
+        B.append(backbone[kb].detach().to('cpu', f32).contiguous())
+    lins = sorted((int(is_lin.search(k).group(2)), k) for k in lin if is_lin.search(k) and k.endswith('weight'))
+    if [i for i, _ in lins] != [0, 1, 2, 3, 4]:
+        raise PnrfError(f"Lpips: lin needs the five entries 'lin0…weight' .. 'lin4…weight' of {LPIPS_LIN[net]} channels, found {[k for _, k in lins]}")
+    L = []
+    for (i, k), c in zip(lins, LPIPS_LIN[net]):
+        if tuple(lin[k].shape) not in ((1, c, 1, 1), (c,)):
+            raise PnrfError(f'Lpips: {k} has shape {tuple(lin[k].shape)}, expected {(1, c, 1, 1)} or {(c,)}')
+        L.append(lin[k].detach().to('cpu', f32).reshape(c).contiguous())
+    return W, B, L
+
+
+def lpips_tap_dims(net, H, W):
+    """[(rows, columns)] of the five tap planes of an H x W image (pnrf_lpips_tap_dims; host only)."""
+    hw = (C.c_int * 10)()
+    check(_lib.load().pnrf_lpips_tap_dims(str(net).encode(), int(H), int(W), hw), 'pnrf_lpips_tap_dims')
+    return [(hw[2 * k], hw[2 * k + 1]) for k in range(5)]
+
+
+_lpips_workspaces = {}     # (handle, device index, stream, H, W) -> workspace: calls on one stream follow each other, so they may share one
+
+
+class Lpips:
+    """LPIPS 0.1 of image pairs on the device (pnrf_lpips_fwd): ``Lpips(net, backbone, lin)`` with net 'alex' | 'vgg', ``backbone`` the
+    torchvision state dict of the net (or the lpips package's, keys ``net.slice*``) and ``lin`` the lpips package's ``lin`` state dict — each a dict
+    or a path (``lpips_weights``).  The weights are the caller's; nothing is fetched from anywhere."""
+
+    def __init__(self, net, backbone, lin, device=None):
+        W, B, L = lpips_weights(net, backbone, lin)
+        lib = _lib.load()
+        self.net, self.device = net, torch.device('cuda' if device is None else device)
+        n = len(W)
+        shapes = (C.c_int * (4 * n))(*[d for w in W for d in w.shape])
+        dims = (C.c_int * 5)(*[int(l.numel()) for l in L])
+        pw, pb, pl = ((C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]) for ts in (W, B, L))
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.pnrf_lpips_create(net.encode(), pw, pb, shapes, n, pl, dims, C.byref(h)), 'pnrf_lpips_create')
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            try:                                                    # (at interpreter exit the module's globals may be gone already)
+                for k in [k for k in _lpips_workspaces if k[0] == h.value]:
+                    del _lpips_workspaces[k]
+                _lib.load().pnrf_lpips_free(h)
+            except Exception:
+                pass
+
+    def _workspace(self, dev, nb, H, W):
+        key = (self._h.value, dev.index, torch.cuda.current_stream().cuda_stream, H, W)
+        ws = _lpips_workspaces.get(key)
+        if ws is None or ws.numel() * 8 < nb:
+            if len(_lpips_workspaces) >= 16:
+                _lpips_workspaces.clear()
+            ws = _lpips_workspaces[key] = torch.empty((nb + 7) // 8, device=dev, dtype=torch.float64)
+        return ws
+
+    def __call__(self, a, b, normalize=True, return_layers=False, return_maps=False):
+        """d(a, b) of two [H,W,3] fp32 GPU images — or views with a pixel stride above 3, e.g. ``rgbd[:, :3].reshape(H, W, 3)`` — as a 0-d float64
+        device tensor; nothing is read back.  ``return_layers``: also the five per-tap means [5]; ``return_maps``: also the five m_k planes."""
+        lib = _lib.load()
+        if a.dim() != 3 or a.shape[-1] != 3 or a.shape != b.shape:
+            raise PnrfError(f'Lpips: expected two [H,W,3] images of one shape, got {tuple(a.shape)} and {tuple(b.shape)}')
+        H, W = int(a.shape[0]), int(a.shape[1])
+        lo = LPIPS_MIN[self.net]
+        if not (lo <= H <= LPIPS_MAX_DIM and lo <= W <= LPIPS_MAX_DIM):
+            raise PnrfError(f'Lpips: {self.net!r} takes images of {lo} .. {LPIPS_MAX_DIM} pixels per side, got {H} x {W}')
+        a, sa, _ = _pixels(a, 'a', 3)
+        b, sb, _ = _pixels(b, 'b', 3)
+        if a.device != b.device:
+            raise PnrfError('Lpips: a and b are on different devices')
+        with torch.cuda.device(a.device):
+            nb = int(lib.pnrf_lpips_workspace_bytes(self._h, H, W))
+            ws = self._workspace(a.device, nb, H, W)
+            out = torch.empty(6, device=a.device, dtype=torch.float64)
+            maps, dims = None, None
+            if return_maps:
+                dims = lpips_tap_dims(self.net, H, W)
+                maps = torch.empty(sum(h * w for h, w in dims), device=a.device, dtype=f32)
+            check(lib.pnrf_lpips_fwd(self._h, _ptr(a), sa, _ptr(b), sb, H, W, int(bool(normalize)), _ptr(out), _ptr(maps), _ptr(ws), nb, _stream()),
+                  'pnrf_lpips_fwd')
+        res = [out[0]]
+        if return_layers:
+            res.append(out[1:])
+        if return_maps:
+            offs = np.cumsum([0] + [h * w for h, w in dims])
+            res.append([maps[offs[k]:offs[k + 1]].view(*dims[k]) for k in range(5)])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def layer(self, layer, x, pool_first=False):
+        """Conv layer ``layer`` of the net (with ``pool_first`` its preceding max pooling first), bias and ReLU on a dense NHWC pair
+        x [2,H,W,C_in] -> [2,OH,OW,C_out] (pnrf_lpips_layer_fwd: the kernels of the metric, for tests)."""
+        lib = _lib.load()
+        shapes = LPIPS_CONVS[self.net]
+        if not 0 <= layer < len(shapes):
+            raise PnrfError(f'Lpips.layer: layer {layer} outside 0 .. {len(shapes) - 1}')
+        co, ci, k, _ = shapes[layer]
+        x = _chk(x, 'x', (ci,))
+        if x.dim() != 4 or x.shape[0] != 2:
+            raise PnrfError(f'Lpips.layer: expected x of shape [2,H,W,{ci}], got {tuple(x.shape)}')
+        H, W = int(x.shape[1]), int(x.shape[2])
+        stride, pad = (4, 2) if k == 11 else (1, k // 2)
+        window = {('alex', 1): 3, ('alex', 2): 3}.get((self.net, layer), 2)
+        h, w = ((H - window) // 2 + 1, (W - window) // 2 + 1) if pool_first else (H, W)
+        oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        with torch.cuda.device(x.device):
+            nb = int(lib.pnrf_lpips_layer_workspace_bytes(self._h, layer, int(pool_first), H, W))
+            ws = torch.empty(max(nb, 8) // 4, device=x.device, dtype=f32)
+            y = torch.empty(2, max(oh, 0), max(ow, 0), co, device=x.device, dtype=f32)
+            check(lib.pnrf_lpips_layer_fwd(self._h, layer, int(pool_first), _ptr(x), H, W, _ptr(y), _ptr(ws), nb, _stream()), 'pnrf_lpips_layer_fwd')
+        return y
+
+
 def patch_indices(nv, H, W, patch, count, generator=None, device=None):
     """Ray indices [count patch^2] (int64, on the device) of ``count`` ``patch`` x ``patch`` crops placed uniformly over the views and the
     positions at which a crop lies inside its view: patch-major, row-major inside a patch, in ``TrainSet``'s numbering

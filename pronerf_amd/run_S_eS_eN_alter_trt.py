@@ -379,6 +379,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     ``pnrf_metrics`` takes PSNR and SSIM (helpers:151-197) of every pose against ``gt_imgs[i]`` from one ``ops.image_metrics`` call on the
     rendered rows, read back together, into ``render_kwargs['psnrs']`` / ``['ssims']``; ``pnrf_device_to8b`` encodes a pose's two PNGs
     from ``ops.frame_to8b``'s uint8 planes (same bytes as ``to8b`` on the host).  The returned float arrays are the same either way.
+    ``pnrf_lpips`` (an ``ops.Lpips``) takes LPIPS of every pose against ``gt_imgs[i]`` on the rendered rows, into ``render_kwargs['lpips']``.
 
     ``pnrf_scene_cache`` = 'f32' | 'u8' (opt-in as well) keeps the source views on the device (``ops.Scene``, built once from ``images`` / ``poses`` /
     ``ref_K``) and renders every pose with ``Renderer.render_pose``: neighbour ranking, projection matrices, neighbour texels and rays are kernels
@@ -397,6 +398,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     dev = next(render_kwargs['network_fine'].parameters()).device
     rgbs0, rgbs1, depths, psnrs, times, walls = [], [], [], [], [], []
     dev_metrics, dev_to8b, ssims = bool(render_kwargs.get('pnrf_metrics')), bool(render_kwargs.get('pnrf_device_to8b')), []
+    lpips_fn, lpips_vals = render_kwargs.get('pnrf_lpips'), []
     from concurrent.futures import ThreadPoolExecutor
     from .dist import FrameGather, world as _world
     from .render import RayPartition
@@ -493,6 +495,8 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
                     psnrs.append(float(mse2psnr(m[1]))); ssims.append(float(m[3]))
                 else:
                     psnrs.append(mse2psnr(img2mse(rgb1, torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev))))
+                if lpips_fn is not None:     # ops.Lpips on the rendered rows where they lie (gt first, as the reference's rgb_lpips(gt, im))
+                    lpips_vals.append(float(lpips_fn(torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev), rgb1)))
             if png_pool is not None:
                 os.makedirs(savedir, exist_ok=True)
                 if dev_to8b:         # the two 8-bit planes come from the device into pinned memory: 4 bytes per pixel instead of 16, no to8b / np.max on the host
@@ -521,6 +525,10 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         if len(ssims) > 0 and verbose:
             print(f'Mean Test SSIM {sum(ssims) / len(ssims)}')
         render_kwargs['ssims'] = ssims
+    if lpips_fn is not None:
+        if len(lpips_vals) > 0 and verbose:
+            print(f'Mean Test LPIPS ({lpips_fn.net}) {sum(lpips_vals) / len(lpips_vals)}')
+        render_kwargs['lpips'] = lpips_vals
     return np.stack(rgbs0, 0), np.stack(rgbs1, 0), np.stack(depths, 0), np.stack(depths, 0)
 
 
@@ -529,6 +537,20 @@ def config_parser():
     """Options of the inference script (run_S_eS_eN_alter_trt.py:44-183); see ``pronerf_amd.config``."""
     from .config import config_parser as _cp
     return _cp('trt')
+
+
+def lpips_from_args(args, device):
+    """The ``ops.Lpips`` of ``--metrics psnr,ssim,lpips``: net ``--lpips_net`` from the files ``--lpips_backbone`` and ``--lpips_lin``.  A missing option or
+    file is a PnrfError here, before a frame is rendered; nothing is fetched."""
+    from .run_nerf_helpers import init_lpips
+    net = getattr(args, 'lpips_net', 'vgg') or 'vgg'
+    paths = {k: getattr(args, k, None) for k in ('lpips_backbone', 'lpips_lin')}
+    for k, p in paths.items():
+        if not p or not os.path.isfile(p):
+            tv = {'alex': 'alexnet', 'vgg': 'vgg16'}.get(net, net)
+            raise PnrfError(f"--metrics …lpips needs --{k}: got {p!r}, which is no file.  Bring the torchvision {tv} state dict (--lpips_backbone) and the lpips "
+                            f"package's weights/v0.1/{net}.pth (--lpips_lin); this package fetches nothing")
+    return init_lpips(net, device, backbone=paths['lpips_backbone'], lin=paths['lpips_lin'])
 
 
 def train(argv=None, device='cuda'):
@@ -589,9 +611,11 @@ def train(argv=None, device='cuda'):
     kw.update({'near': near, 'far': far, 'images': images[i_ref], 'poses': poses[i_ref], 'ref_K': K})   # :773-787
     kw['pnrf_preset'] = getattr(args, 'pnrf_preset', 'default')
     metrics = [m for m in str(getattr(args, 'metrics', 'psnr')).split(',') if m]
-    if not set(metrics) <= {'psnr', 'ssim'}:
-        raise PnrfError(f"--metrics takes 'psnr' or 'psnr,ssim', got {args.metrics!r}")
+    if not set(metrics) <= {'psnr', 'ssim', 'lpips'}:
+        raise PnrfError(f"--metrics takes 'psnr', 'psnr,ssim' or 'psnr,ssim,lpips', got {args.metrics!r}")
     kw['pnrf_metrics'] = 'ssim' in metrics
+    if 'lpips' in metrics:
+        kw['pnrf_lpips'] = lpips_from_args(args, device)        # raises before anything is rendered when a weight file is missing
     kw['pnrf_device_to8b'] = bool(getattr(args, 'device_to8b', False))
     if getattr(args, 'scene_cache', None) not in (None, 'None', 'off'):
         kw['pnrf_scene_cache'] = args.scene_cache

@@ -13,6 +13,7 @@ Same names, argument meaning and error behaviour as the live subset of the refer
     get_rays / ndc_rays            helpers:2705-2714, 2776-2793 -> pnrf_frame_rays_fwd / pnrf_ndc_rays_fwd
     img2ssim                       helpers:151-197   -> pnrf_image_metrics_fwd
     img2ssim gradient              (autograd of :151-197) -> pnrf_ssim_loss_fwd  (ops.ssim_loss, autograd.ssim)
+    init_lpips / rgb_lpips         helpers:137-149   -> pnrf_lpips_create / pnrf_lpips_fwd  (ops.Lpips; the weights are the caller's)
 
 The model classes keep the reference's ``state_dict`` keys (``fc_backbone.{i}.*``, ``fc_output.*``,
 ``layers.{i}.*``) so checkpoints interchange; their parameters are re-packed into the device weight
@@ -53,6 +54,35 @@ def img2ssim(img0, img1, max_val=1, filter_size=11, filter_sigma=1.5, k1=0.01, k
     if return_map:
         return res[1].cpu().numpy() if host else res[1]
     return float(res[3])
+
+
+__LPIPS__ = {}
+LPIPS_WEIGHTS = {}      # net_name -> (backbone, lin): state dicts or paths that init_lpips uses when it is called with the reference's two arguments
+
+
+def init_lpips(net_name, device, backbone=None, lin=None):
+    """``lpips.LPIPS(net=net_name, version='0.1')`` of the reference (helpers:138-142) as an ``ops.Lpips`` on ``device``.  The reference's package
+    downloads its weights; nothing here fetches anything: ``backbone`` (the torchvision state dict of the net, or the lpips package's) and ``lin``
+    (the lpips package's ``lin`` state dict) are the caller's — dicts or paths, given here or registered in ``LPIPS_WEIGHTS[net_name]``."""
+    if net_name not in ('alex', 'vgg'):
+        raise PnrfError(f"init_lpips: net_name {net_name!r}; the kernels take 'alex' and 'vgg'")
+    if backbone is None and lin is None and net_name in LPIPS_WEIGHTS:
+        backbone, lin = LPIPS_WEIGHTS[net_name]
+    if backbone is None or lin is None:
+        tv = {'alex': 'alexnet', 'vgg': 'vgg16'}[net_name]
+        raise PnrfError(f'init_lpips: no weights for {net_name!r}.  Bring two files: the torchvision {tv} state dict (backbone=, --lpips_backbone) and the lpips '
+                        f"package's weights/v0.1/{net_name}.pth (lin=, --lpips_lin); this package fetches nothing")
+    print(f'init_lpips: lpips_{net_name}')
+    return ops.Lpips(net_name, backbone, lin, device=device)
+
+
+def rgb_lpips(np_gt, np_im, net_name, device, normalize=True):
+    """LPIPS of two [H,W,3] numpy images as a Python float (helpers:144-149) -> pnrf_lpips_fwd."""
+    if net_name not in __LPIPS__:
+        __LPIPS__[net_name] = init_lpips(net_name, device)
+    gt = torch.from_numpy(np.ascontiguousarray(np_gt, dtype=np.float32)).to(device)
+    im = torch.from_numpy(np.ascontiguousarray(np_im, dtype=np.float32)).to(device)
+    return __LPIPS__[net_name](gt, im, normalize=normalize).item()
 
 
 # ------------------------------------------------------------------------------- encodings
