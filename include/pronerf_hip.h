@@ -653,6 +653,49 @@ int pnrf_lpips_fwd(const pnrf_lpips_t* h, const float* a, int a_stride, const fl
 int64_t pnrf_lpips_layer_workspace_bytes(const pnrf_lpips_t* h, int layer, int pool_first, int H, int W);
 int pnrf_lpips_layer_fwd(const pnrf_lpips_t* h, int layer, int pool_first, const float* x, int H, int W, float* y, void* workspace,
                          int64_t workspace_bytes, void* stream);
+/* LPIPS as a training loss: the mean d of B patch pairs of H x W x 3 and its gradient with respect to the prediction.
+ * pred, gt: dev fp32, patch b pixel (y, x) channel c at [b patch_stride + (y W + x) stride + c], strides as pnrf_ssim_loss_fwd (pixel stride >= 3
+ * floats; patch stride >= 0, 0 reads one patch B times).  Sides as pnrf_lpips_fwd (alex >= 31, vgg >= 16, <= PNRF_LPIPS_MAX_DIM), B >= 1, and
+ * 2 B H W <= 2^31 - 1 (the kernels' pixel index).
+ * Definition: that of pnrf_lpips_fwd per pair.  The B pairs run as one batch of 2 B images [pred_0 .. pred_{B-1}, gt_0 .. gt_{B-1}];
+ * out: dev double[6] = {mean over the patches of d, the five tap means over patches and pixels}.  On numbers the forward arithmetic is that of
+ * pnrf_lpips_fwd: for B = 1 the six numbers have that call's bits.  A NaN in a patch is kept (the loss's own conv and pooling kernels: ReLU and
+ * maximum as torch takes them), so the value is NaN; the metric's kernels drop it.
+ * d_pred: dev fp32 [B,H,W,3], dense = d out[0] / d pred.  The weight and the sign are the caller's.
+ * Backward, pred half only, top layer down, with omega_k = 1 / (B h_k w_k), F the pred features of a tap pixel, s = sqrt(sum_c F_c^2),
+ * na = F / (s + 1e-10), nb likewise from gt:  r_c = 2 omega_k lin_c (na - nb)_c,  dF_c = (r_c - na_c (sum_j r_j F_j) / s) / (s + 1e-10), sums over the
+ * channels as a butterfly over the wave; it is added to the gradient arriving from the layers above.  ReLU: dz = dy [y > 0].  Convolutions with
+ * C_in >= 64: dX = dZ * flip(W)^T as an implicit GEMM on the exact-fp32 MFMA, sums in (k-1-ky, k-1-kx, c_out) order — with few pixels (at most 32 workgroups of 64 pixels x 64 channels) one chain per filter tap and the taps' sums
+ * added in tap order by a second kernel, a function of the shape alone; first layers: per input value a
+ * gather over the outputs whose window covers it, one fmaf chain in (oy, ox, c_out) order, then x 2 / scale_c (normalize) or 1 / scale_c.
+ * Max pooling: per input element a gather over the windows that hold it, in row-major order.
+ * Kink rules.  ReLU: y == 0 gives 0, as torch.  Tap: at s == 0 the second term of dF is taken as 0 (float64 autograd gives NaN from sqrt'(0)); the
+ * ReLU mask zeroes that pixel anyway.  Tie rule of the pooling: the gradient of a window goes to the first element attaining its maximum in
+ * (ky, kx) order, as torch's CPU kernel; elements in the rows / columns that the floor sizes drop get exactly 0.
+ * No atomics, one writer per element, every sum in a fixed order: value and gradient are bit-identical from call to call on any stream; patches
+ * do not see each other (a NaN in one stays in its gradient, and reaches the value).  pred == gt gives exactly 0 and a gradient of exactly 0.
+ * workspace: dev, 16-byte aligned, >= pnrf_lpips_loss_workspace_bytes(h, B, H, W) bytes (every conv output of the batch, two gradient buffers, the
+ * partial sums), contents irrelevant; concurrent calls need separate workspaces.  The first pnrf_lpips_loss_workspace_bytes (or
+ * pnrf_lpips_layer_bwd_workspace_bytes) on a handle packs its weights a second time for the data gradient, [k k C_out][C_in] flipped (one device
+ * allocation, waited for): make it outside a stream capture; a handle used for the metric alone never pays it.  pnrf_lpips_loss_fwd itself
+ * allocates nothing and reads nothing back: it is capturable in a hipGraph.  Everything outside the limits above, a null pointer or a short
+ * workspace return PNRF_E_ARG before any launch, and pnrf_lpips_loss_workspace_bytes returns 0 for such sizes. */
+int64_t pnrf_lpips_loss_workspace_bytes(const pnrf_lpips_t* h, int B, int H, int W);
+int pnrf_lpips_loss_fwd(const pnrf_lpips_t* h, const float* pred, int pred_stride, int64_t pred_patch_stride, const float* gt, int gt_stride,
+                        int64_t gt_patch_stride, int B, int H, int W, int normalize, double* out, float* d_pred, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* For tests: the backward of conv layer `layer` — with pool_first its preceding max pooling in front — on n images, by the kernels the loss runs.
+ * x: dev fp32 [n,H,W,C_in] the saved input (the pooling's input with pool_first), y: [n,OH,OW,C_out] the saved output (after ReLU), dy: its
+ * gradient, all dense NHWC and 16-byte aligned -> dx [n,H,W,C_in] = pooling gather(data gradient(dy [y > 0])); layer 0: lpips_dgrad0_kernel
+ * without the input scaling.  The first mask is a kernel of this entry point alone (in the loss the kernel that writes a gradient applies it);
+ * relu_in != 0 (hidden layers): dx is also multiplied by [x > 0] in the data gradient's epilogue / the pooling gather, as the loss does it.
+ * workspace: >= pnrf_lpips_layer_bwd_workspace_bytes bytes (0 for what the call refuses). */
+int64_t pnrf_lpips_layer_bwd_workspace_bytes(const pnrf_lpips_t* h, int layer, int pool_first, int n, int H, int W);
+int pnrf_lpips_layer_bwd(const pnrf_lpips_t* h, int layer, int pool_first, int relu_in, int n, const float* x, int H, int W, const float* y,
+                         const float* dy, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
+/* For tests: the tap backward alone.  f_pred, f_gt: dev fp32 [P, C_tap] features of P = n h w tap pixels (omega = 1 / P) -> d_f [P, C_tap] =
+ * dF [F > 0], F = f_pred: the gradient with respect to the pre-activation, as the loss stores it. */
+int pnrf_lpips_tap_bwd(const pnrf_lpips_t* h, int tap, const float* f_pred, const float* f_gt, int64_t P, float* d_f, void* stream);
 
 /* ---- device-resident scene: a frame from a camera pose alone ---------------------------------------
  * What render_path does per pose on the host (run_S_eS_eN_alter_trt.py:245-302: rank the source cameras, fetch / permute / upload the neighbour

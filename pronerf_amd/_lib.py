@@ -87,6 +87,11 @@ SIGNATURES = {
     'pnrf_lpips_fwd': (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     'pnrf_lpips_layer_workspace_bytes': (_i64, [_p, _i, _i, _i, _i]),
     'pnrf_lpips_layer_fwd': (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _i64, _p]),
+    'pnrf_lpips_loss_workspace_bytes': (_i64, [_p, _i, _i, _i]),
+    'pnrf_lpips_loss_fwd': (_i, [_p, _p, _i, _i64, _p, _i, _i64, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
+    'pnrf_lpips_layer_bwd_workspace_bytes': (_i64, [_p, _i, _i, _i, _i, _i]),
+    'pnrf_lpips_layer_bwd': (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _i64, _p]),
+    'pnrf_lpips_tap_bwd': (_i, [_p, _i, _p, _p, _i64, _p, _p]),
     # device-resident scene: pose -> frame
     'pnrf_scene_create': (_i, [_i, _i, _i, _i, C.POINTER(_p)]),
     'pnrf_scene_free': (_i, [_p]),

@@ -15,7 +15,8 @@ after any other trainer call, raises ``PnrfError`` with the library's PNRF_E_STA
 respect to rays or images.
 
 ``ssim`` is the mean img2ssim of image patches as a differentiable scalar (``ops.ssim_loss``: value and gradient from one kernel pair), for
-a structural term in such a loss when the batch is made of patches (the stage-2 driver's ``patch_size``).
+a structural term in such a loss when the batch is made of patches (the stage-2 driver's ``patch_size``).  ``lpips`` is the mean LPIPS of such
+patches in the same mould (``ops.Lpips.loss``), the perceptual term of the stage-2 driver's ``--a_p``.
 """
 from __future__ import annotations
 
@@ -67,6 +68,26 @@ def ssim(pred, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.
     such as ``mse + lam * (1 - ssim(pred, gt))``.  The gradient is computed with the value and kept; backward is one multiply by the incoming
     gradient, without a host sync.  ``gt`` gets none; no second-order gradients."""
     return _Ssim.apply(pred, gt, dict(max_val=max_val, filter_size=filter_size, filter_sigma=filter_sigma, k1=k1, k2=k2))
+
+
+class _Lpips(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, lp, normalize):
+        value, d_pred = lp.loss(pred, gt, normalize=normalize)
+        ctx.save_for_backward(d_pred)                    # value and gradient come from one call: backward has nothing to launch but a product
+        return value.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad):
+        d_pred, = ctx.saved_tensors
+        return grad * d_pred, None, None, None           # no gradient with respect to gt
+
+
+def lpips(pred, gt, lp, normalize=True):
+    """Mean LPIPS of [B,H,W,3] or [H,W,3] patches under the ``ops.Lpips`` handle ``lp`` (``Lpips.loss``) as a float32 scalar, differentiable
+    with respect to ``pred`` — for a loss such as ``mse + a_p * lpips(pred, gt, lp)``.  The gradient is computed with the value and kept;
+    backward is one multiply by the incoming gradient, without a host sync.  ``gt`` gets none; no second-order gradients."""
+    return _Lpips.apply(pred, gt, lp, bool(normalize))
 
 
 def render_train(trainer, rays, or_rays, img4, poses, K, ref_nos, jitter=None, jitter_dir=1, raw_noise=None, white_bkgd=False, eps=1e-5, clamp=0.0,

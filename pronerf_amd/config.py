@@ -52,7 +52,9 @@ _VARIANT = {
             # pnrf_scene_cache; 'u8': RGBA8 texels, for images that are exact 8-bit values)
             ('scene_cache', str, None)],
     # stage 2 (run_S_eS_eN_alter_base_refine2.py)
-    'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)] + _TRAIN,
+    # (lpips_*: the net and the two weight files of the perceptual term a_p, as the inference script's --metrics lpips takes them)
+    'refine2': [('basedir', str, './logs_epi_RR/'), ('pretrain_path', str, None), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None),
+                ('lpips_net', str, 'vgg'), ('lpips_backbone', str, None), ('lpips_lin', str, None)] + _TRAIN,
     # stage 1 (run_S_eS_eN_alter_base.py)
     'base': [('basedir', str, './logs_epi_RR/'), ('epi_nerf', 'flag', False), ('test_frames', 'ints', [3, 11]), ('max_steps', int, None)] + _TRAIN,
 }

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 
 #include "pnrf_common.h"
 #include "pnrf_ieee.h"
@@ -30,6 +31,10 @@ struct pnrf_lpips {
   float* d_b[13];
   float* d_lin[5];
   int device;
+  // the loss: every hidden layer's weights a second time, flipped and transposed for the data gradient, [k k C_out][C_in]; made by the first loss call
+  std::mutex mu;
+  float* d_wt_all;
+  float* d_wt[13];
 };
 
 namespace {
@@ -434,7 +439,7 @@ extern "C" int pnrf_lpips_create(const char* net, const float* const* conv_w, co
     if (rc) return rc;
   }
   pnrf_lpips* h = new pnrf_lpips();
-  h->net = id; h->n = n; h->d_all = nullptr;
+  h->net = id; h->n = n; h->d_all = nullptr; h->d_wt_all = nullptr;
   hipError_t e = hipGetDevice(&h->device);
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_all, total * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(h->d_all, img.data(), total * sizeof(float), hipMemcpyHostToDevice);
@@ -453,6 +458,7 @@ extern "C" int pnrf_lpips_create(const char* net, const float* const* conv_w, co
 extern "C" int pnrf_lpips_free(pnrf_lpips_t* h) {
   if (!h) return 0;
   if (h->d_all) (void)hipFree(h->d_all);
+  if (h->d_wt_all) (void)hipFree(h->d_wt_all);
   delete h;
   return 0;
 }
@@ -550,3 +556,6 @@ extern "C" int pnrf_lpips_layer_fwd(const pnrf_lpips_t* h, int layer, int pool_f
   int oh, ow;
   return run_layer(h, layer, pool_first != 0, x, x + (int64_t)H * W * 3, 3, 3, 0, H, W, (float*)workspace, y, &oh, &ow, (hipStream_t)stream);
 }
+
+// ---- the loss: value and gradient (pnrf_lpips_loss_fwd, pnrf_lpips_layer_bwd, pnrf_lpips_tap_bwd) -------------------------------------------------
+#include "pnrf_lpips_loss.h"

@@ -975,6 +975,78 @@ class Lpips:
             check(lib.pnrf_lpips_layer_fwd(self._h, layer, int(pool_first), _ptr(x), H, W, _ptr(y), _ptr(ws), nb, _stream()), 'pnrf_lpips_layer_fwd')
         return y
 
+    def loss(self, pred, gt, normalize=True, return_layers=False):
+        """The mean d(pred_i, gt_i) of B patch pairs and its gradient with respect to ``pred`` (pnrf_lpips_loss_fwd).  ``pred`` / ``gt``:
+        [B,H,W,3] or [H,W,3] fp32 GPU tensors; views with a pixel stride above 3 and any patch stride are read in place.  Returns (mean d as a
+        0-d float64 device tensor, d mean / d pred as a float32 tensor shaped like ``pred``) — nothing is read back; ``return_layers``: also
+        the five tap means [5].  The weight and the sign are the caller's (``autograd.lpips`` makes it differentiable)."""
+        lib = _lib.load()
+        if pred.dim() not in (3, 4) or pred.shape[-1] != 3 or pred.shape != gt.shape:
+            raise PnrfError(f'Lpips.loss: expected two [B,H,W,3] or [H,W,3] tensors of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}')
+        shape = tuple(pred.shape)
+        B, H, W = (1,) * (pred.dim() == 3) + tuple(int(x) for x in shape[:-1])
+        lo = LPIPS_MIN[self.net]
+        if not (lo <= H <= LPIPS_MAX_DIM and lo <= W <= LPIPS_MAX_DIM) or B < 1 or 2 * B * H * W > 2 ** 31 - 1:
+            raise PnrfError(f'Lpips.loss: {self.net!r} takes B >= 1 patches of {lo} .. {LPIPS_MAX_DIM} pixels per side with 2 B H W < 2^31, got {B} of {H} x {W}')
+        pred, sp, pp = _patches(pred.reshape(B, H, W, 3) if pred.dim() == 3 else pred, 'pred')
+        gt, sg, pg = _patches(gt.reshape(B, H, W, 3) if gt.dim() == 3 else gt, 'gt')
+        if gt.device != pred.device:
+            raise PnrfError('Lpips.loss: pred and gt are on different devices')
+        with torch.cuda.device(pred.device):
+            nb = int(lib.pnrf_lpips_loss_workspace_bytes(self._h, B, H, W))
+            if nb <= 0:
+                check(-1, 'pnrf_lpips_loss_workspace_bytes')
+            ws = self._workspace(pred.device, nb, ('loss', B, H), W)
+            out = torch.empty(6, device=pred.device, dtype=torch.float64)
+            d_pred = torch.empty(shape, device=pred.device, dtype=f32)
+            check(lib.pnrf_lpips_loss_fwd(self._h, _ptr(pred), sp, pp, _ptr(gt), sg, pg, B, H, W, int(bool(normalize)), _ptr(out), _ptr(d_pred), _ptr(ws), nb,
+                                          _stream()), 'pnrf_lpips_loss_fwd')
+        return (out[0], d_pred, out[1:]) if return_layers else (out[0], d_pred)
+
+    def _geometry(self, layer, H, W, pool_first):
+        co, ci, k, _ = LPIPS_CONVS[self.net][layer]
+        stride, pad = (4, 2) if k == 11 else (1, k // 2)
+        window = {('alex', 1): 3, ('alex', 2): 3}.get((self.net, layer), 2)
+        h, w = ((H - window) // 2 + 1, (W - window) // 2 + 1) if pool_first else (H, W)
+        return co, ci, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+    def layer_bwd(self, layer, x, y, dy, pool_first=False, relu_in=False):
+        """The backward of ``layer`` (``Lpips.layer``'s arguments) on n images: x [n,H,W,C_in] the saved input, y [n,OH,OW,C_out] the saved output,
+        dy its gradient -> dx [n,H,W,C_in] (pnrf_lpips_layer_bwd: the kernels of the loss, for tests).  ``relu_in``: dx is also multiplied by
+        [x > 0], in the kernel that writes it."""
+        lib = _lib.load()
+        shapes = LPIPS_CONVS[self.net]
+        if not 0 <= layer < len(shapes):
+            raise PnrfError(f'Lpips.layer_bwd: layer {layer} outside 0 .. {len(shapes) - 1}')
+        x = _chk(x, 'x', (shapes[layer][1],))
+        if x.dim() != 4:
+            raise PnrfError(f'Lpips.layer_bwd: expected x of shape [n,H,W,{shapes[layer][1]}], got {tuple(x.shape)}')
+        n, H, W = (int(v) for v in x.shape[:3])
+        co, ci, oh, ow = self._geometry(layer, H, W, pool_first)
+        y, dy = _chk(y, 'y', (co,)), _chk(dy, 'dy', (co,))
+        if tuple(y.shape) != (n, oh, ow, co) or y.shape != dy.shape:
+            raise PnrfError(f'Lpips.layer_bwd: expected y and dy of shape {(n, oh, ow, co)}, got {tuple(y.shape)} and {tuple(dy.shape)}')
+        with torch.cuda.device(x.device):
+            nb = int(lib.pnrf_lpips_layer_bwd_workspace_bytes(self._h, layer, int(pool_first), n, H, W))
+            ws = torch.empty(max(nb, 16) // 4, device=x.device, dtype=f32)
+            dx = torch.empty_like(x)
+            check(lib.pnrf_lpips_layer_bwd(self._h, layer, int(pool_first), int(relu_in), n, _ptr(x), H, W, _ptr(y), _ptr(dy), _ptr(dx), _ptr(ws), nb,
+                                           _stream()), 'pnrf_lpips_layer_bwd')
+        return dx
+
+    def tap_bwd(self, tap, f_pred, f_gt):
+        """dF [F > 0] of tap ``tap`` for features f_pred, f_gt [..., C_tap] of any number of tap pixels P (omega = 1 / P) (pnrf_lpips_tap_bwd: the
+        loss's kernel, for tests)."""
+        lib = _lib.load()
+        c = LPIPS_LIN[self.net][tap]
+        f_pred, f_gt = _chk(f_pred, 'f_pred', (c,)), _chk(f_gt, 'f_gt', (c,))
+        if f_pred.shape != f_gt.shape:
+            raise PnrfError(f'Lpips.tap_bwd: f_pred {tuple(f_pred.shape)} and f_gt {tuple(f_gt.shape)} differ')
+        with torch.cuda.device(f_pred.device):
+            d = torch.empty_like(f_pred)
+            check(lib.pnrf_lpips_tap_bwd(self._h, int(tap), _ptr(f_pred), _ptr(f_gt), f_pred.numel() // c, _ptr(d), _stream()), 'pnrf_lpips_tap_bwd')
+        return d
+
 
 def patch_indices(nv, H, W, patch, count, generator=None, device=None):
     """Ray indices [count patch^2] (int64, on the device) of ``count`` ``patch`` x ``patch`` crops placed uniformly over the views and the

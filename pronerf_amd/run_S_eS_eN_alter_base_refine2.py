@@ -303,6 +303,37 @@ def config_parser():
     return _cp('refine2')
 
 
+def perceptual_loss(args, patch_size, device):
+    """The loss of ``--a_p`` > 0 as a ``loss_fn`` of ``train``: the reference's terms — mse(rgb_map1) + a_mmrgb (mse(rgb_map0) + mse(mm_rgb)) — plus
+    a_p x ``autograd.lpips`` of the batch's rgb_map1 patches against the target patches (normalize=True: both lie in [0, 1]).  Raises ``PnrfError``
+    naming what is missing: a ``patch_size`` of at least the net's smallest side, ``--lpips_net`` alex | vgg, and the two weight files
+    ``--lpips_backbone`` / ``--lpips_lin`` the user brings (``run_nerf_helpers.init_lpips``; nothing is fetched)."""
+    import os
+    from .autograd import lpips
+    from .run_nerf_helpers import init_lpips
+    net = args.lpips_net
+    if net not in ops.LPIPS_MIN:
+        raise PnrfError(f"--a_p {args.a_p}: --lpips_net {net!r}; the kernels take 'alex' and 'vgg'")
+    if patch_size < ops.LPIPS_MIN[net]:
+        raise PnrfError(f'--a_p {args.a_p} needs patch batches: train(..., patch_size=p) with p >= {ops.LPIPS_MIN[net]} for --lpips_net {net} '
+                        f'(got patch_size = {patch_size}); LPIPS is taken of patch_size x patch_size crops')
+    for k in ('lpips_backbone', 'lpips_lin'):
+        path = getattr(args, k)
+        if not path or not os.path.isfile(path):
+            tv = 'alexnet' if net == 'alex' else 'vgg16'
+            raise PnrfError(f"--a_p {args.a_p} needs --{k}: got {path!r}, which is no file.  Bring the torchvision {tv} state dict (--lpips_backbone) and the "
+                            f"lpips package's weights/v0.1/{net}.pth (--lpips_lin); this package fetches nothing")
+    lp = init_lpips(net, device, backbone=args.lpips_backbone, lin=args.lpips_lin)
+    a_p, a_mm, p = float(args.a_p), float(args.a_mmrgb), int(patch_size)
+
+    def loss_fn(maps, target, step):
+        total = ((maps['rgb_map1'] - target) ** 2).mean()
+        if a_mm > 0:
+            total = total + a_mm * (((maps['rgb_map0'] - target) ** 2).mean() + ((maps['mm_rgb'] - target) ** 2).mean())
+        return total + a_p * lpips(maps['rgb_map1'].reshape(-1, p, p, 3), target.reshape(-1, p, p, 3), lp)
+    return loss_fn
+
+
 def train(argv=None, device='cuda', loss_fn=None, patch_size=0):
     """Stage-2 training driver (run_S_eS_eN_alter_base_refine2.py:683-1000): LLFF scene, stage-1 checkpoint (--pretrain_path),
     pre-shuffled ray batches of all training views, one ``Trainer.fwd_bwd`` + ``adam_step`` per iteration with the reference's
@@ -316,7 +347,10 @@ def train(argv=None, device='cuda', loss_fn=None, patch_size=0):
 
     patch_size > 0: every batch is N_rand // patch_size^2 crops of patch_size x patch_size pixels (``ops.patch_indices``) instead of a slice
     of the pixel permutation, for a loss that needs image structure (``autograd.ssim``): the rows of ``maps`` and ``target`` then reshape to
-    [count, patch_size, patch_size, .].  Needs --device_batches rays|all, a single replica and N_rand divisible by patch_size^2."""
+    [count, patch_size, patch_size, .].  Needs --device_batches rays|all, a single replica and N_rand divisible by patch_size^2.
+
+    --a_p > 0 without a ``loss_fn``: the loss is ``perceptual_loss`` — the reference's terms + a_p x LPIPS of the patches — and the iteration the
+    split path above; it needs ``patch_size`` and the --lpips_* options, checked before anything is loaded.  With --a_p 0 (the default) nothing changes."""
     import os
     from .load_llff import load_llff_data
     from .render import N_SAMPLES
@@ -340,6 +374,8 @@ def train(argv=None, device='cuda', loss_fn=None, patch_size=0):
     if patch_size < 0 or (patch_size and (args.device_batches == 'off' or world > 1 or args.N_rand % patch_size ** 2)):
         raise PnrfError(f'patch_size = {patch_size} needs --device_batches rays|all (got {args.device_batches}), a single replica (got {world}) and '
                         f'N_rand divisible by patch_size^2 (N_rand = {args.N_rand})')
+    if args.a_p > 0 and loss_fn is None:                 # the reference's terms + a_p x the mean LPIPS of the batch's patches, through the split path
+        loss_fn = perceptual_loss(args, patch_size, dev)
     images, poses, bds, _, i_test = load_llff_data(args.datadir, args.factor, recenter=True, bd_factor=.75, spherify=args.spherify)
     hwf = poses[0, :3, -1]
     poses = poses[:, :3, :4]

@@ -14,6 +14,7 @@ Same names, argument meaning and error behaviour as the live subset of the refer
     img2ssim                       helpers:151-197   -> pnrf_image_metrics_fwd
     img2ssim gradient              (autograd of :151-197) -> pnrf_ssim_loss_fwd  (ops.ssim_loss, autograd.ssim)
     init_lpips / rgb_lpips         helpers:137-149   -> pnrf_lpips_create / pnrf_lpips_fwd  (ops.Lpips; the weights are the caller's)
+    LPIPS gradient (--a_p)         (autograd of :137-149) -> pnrf_lpips_loss_fwd  (ops.Lpips.loss, autograd.lpips)
 
 The model classes keep the reference's ``state_dict`` keys (``fc_backbone.{i}.*``, ``fc_output.*``,
 ``layers.{i}.*``) so checkpoints interchange; their parameters are re-packed into the device weight
