@@ -96,6 +96,21 @@ int pnrf_mlp_kind(const pnrf_mlp_t* h, int* net, int* in_dim, int* in_dim_x, int
 int pnrf_mlp_pack_image(int net, const float* const* W, const float* const* b, const int* in_dim,
                         const int* out_dim, int n_layers, void* buf, int64_t capacity, int64_t* size);
 int pnrf_mlp_skips(const pnrf_mlp_t* h, uint32_t* mask);
+/* Repack a handle in place, on the device, from weights that live on the device: W[l] / b[l] are DEVICE pointers (torch layout W[out, in], layer order
+ * of pnrf_mlp_pack); the arrays of pointers and dims are host arrays.  Kernels on `stream` rewrite every weight-dependent buffer of the handle — all its
+ * weight streams, the bias tables, the pass-1 constants — at the same device addresses, to the bytes pnrf_mlp_pack_image writes for these weights (the
+ * kernels and the host packer share one statement of the element rules; only NaN payloads may differ).  Maps, ray points, variant and shape settings are
+ * left alone, so contexts, scenes and captured graphs that hold the handle's buffers stay valid.
+ * The weights must have the handle's shape (net kind, hidden layers, ray points, neighbour views, skip mask; a deserialized handle serves as well):
+ * PNRF_E_SHAPE otherwise, PNRF_E_ARG for a null pointer, PNRF_E_STATE for a handle of another device than the current one — all decided on the host before
+ * anything is launched: a refused call leaves the handle untouched.
+ * The call never synchronises with the host.  The first call on a handle allocates and uploads a small plan (the packer's per-layer tables, scratch for
+ * the folded matrices), owned by the handle and freed by pnrf_mlp_free; later calls allocate and copy nothing and can be captured in a hipGraph on one
+ * stream (the weight pointers are kernel arguments: a captured call reads the addresses it was captured with).
+ * ORDERING: the rewrite is ordered against renders that use the handle by stream order alone, and that is the caller's business — run it on the stream
+ * the handle's launches run on, or order the streams with events.  The weights are read when the kernels run, not when the call returns. */
+int pnrf_mlp_repack(pnrf_mlp_t* h, const float* const* W, const float* const* b, const int* in_dim,
+                    const int* out_dim, int n_layers, void* stream);
 
 /* Kernel variant of a packed network.  PNRF_VARIANT_DEFAULT is what pack / deserialize produce and what every product path runs:
  * sampler with the folded first layer in split fp16 (fp32-grade, three v_mfma_f32_16x16x32_f16 per product) — through pnrf_sampler_fwd_ws /
@@ -468,6 +483,11 @@ int pnrf_trainer_set_step(pnrf_trainer_t* t, int64_t step, int64_t step_nerf);
 /* Device address / element count of a flat array (kind as above): layers contiguous in trainer order, each [W, b] padded to 4
  * floats.  For in-place collectives over data-parallel replicas (RCCL all-reduce of the gradients). */
 int pnrf_trainer_flat(pnrf_trainer_t* t, int kind, float** ptr, int64_t* count);
+/* Trainer -> renderable nets without leaving the device: pnrf_mlp_repack of each non-NULL handle from the trainer's own parameters (sampler: trainer
+ * layers 0-6, refine: 7-13, fine: 14-25 = the NeRF class in pack order pts0..7, feature, alpha, views, rgb), on `stream`.  Reads only: trainer state is
+ * not changed, and the call may stand between pnrf_train_stage2_fwd and _bwd.  A handle of another kind or shape (fine: anything but PNRF_NET_NERFCLS)
+ * is refused as by pnrf_mlp_repack, before anything is launched for any of the three.  Ordering against training steps and renders: stream order. */
+int pnrf_trainer_publish(const pnrf_trainer_t* t, pnrf_mlp_t* sampler, pnrf_mlp_t* refine, pnrf_mlp_t* fine, void* stream);
 
 typedef struct pnrf_train_batch {
   const float* rays;       /* dev [n,11] NDC ray batch (o, d, near, far, viewdir) */

@@ -32,6 +32,7 @@ SIGNATURES = {
     'pnrf_last_error': (C.c_char_p, []),
     'pnrf_mlp_pack': (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_p)]),
     'pnrf_mlp_pack_image': (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p, _i64, C.POINTER(_i64)]),
+    'pnrf_mlp_repack': (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p]),
     'pnrf_mlp_free': (_i, [_p]),
     'pnrf_mlp_serialize': (_i, [_p, _p, _i64, C.POINTER(_i64)]),
     'pnrf_mlp_deserialize': (_i, [_p, _i64, C.POINTER(_p)]),
@@ -124,6 +125,7 @@ SIGNATURES = {
     'pnrf_trainer_set_graph': (_i, [_p, _i]),
     'pnrf_trainer_set_products': (_i, [_p, _i]),
     'pnrf_trainer_flat': (_i, [_p, _i, C.POINTER(_p), C.POINTER(_i64)]),
+    'pnrf_trainer_publish': (_i, [_p, _p, _p, _p, _p]),
     'pnrf_train_stage2_fwd_bwd': (_i, [_p, _p, _p, _p, _p]),
     'pnrf_train_explore_fwd_bwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),
     'pnrf_train_stage2_fwd': (_i, [_p, _p, _p, _p]),

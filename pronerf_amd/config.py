@@ -34,7 +34,9 @@ _COMMON = [
 # not in the reference, both training scripts: where a batch is assembled.  'off': per-pixel arrays of every training view, gathered per iteration (the
 # statements of the first release); 'rays': rays, targets and neighbour views from a device-resident scene and the batch's ray indices
 # (ops.TrainSet), jitter and noise from torch as before; 'all': jitter and noise from the device generator too, seeded by batch_seed
-_TRAIN = [('device_batches', ('off', 'rays', 'all'), 'off'), ('batch_seed', int, 0)]
+# testset_path: the periodic hold-out render on the training-time forward kernels ('train', the statements of the first release) or through a Renderer
+# that follows the trainer on the device ('render': evaluate_views(path='render'), the fused inference kernels)
+_TRAIN = [('device_batches', ('off', 'rays', 'all'), 'off'), ('batch_seed', int, 0), ('testset_path', ('train', 'render'), 'train')]
 _VARIANT = {
     # inference (run_S_eS_eN_alter_trt.py): TensorRT / ONNX switches are parsed for config compatibility only
     'trt': [('basedir', str, './logs_trt/'), ('use_trt', 'flag', False), ('export_only', 'flag', False), ('nerf_engine_path', str, None),

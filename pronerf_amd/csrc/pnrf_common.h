@@ -8,6 +8,7 @@
 
 #include "../../include/pronerf_hip.h"
 #include "pnrf_layout.h"
+#include "pnrf_pack_rules.h"
 
 namespace pnrf {
 
@@ -39,9 +40,25 @@ void set_error(const char* fmt, ...);
     }                                                                                    \
   } while (0)
 
+// The device plan of a handle (built by its first pnrf_mlp_repack, freed by pnrf_mlp_free; not a section of the engine image): per weight stream and
+// bias table the layers' tables the host packer builds (PackEntry, pnrf_pack_rules.h), the maps they index, the derive ops and their scratch
+struct RepackJob { char* dst; int first, count, max_frags; };      // a section of the handle and its entries [first, first + count)
+struct RepackPlan {
+  std::vector<RepackJob> jobs;
+  PackEntry* d_entries = nullptr;
+  int* d_maps = nullptr;
+  DeriveOp* d_ops = nullptr;
+  int n_ops = 0, max_elems = 0;
+  std::vector<void*> allocs;                            // every device allocation of the plan
+  std::vector<std::pair<void*, size_t>> scratch;        // the derived matrices (zero-filled on the stream of the first repack)
+  bool fresh = true;
+};
+// pnrf_pack.hip: every host-side check of pnrf_mlp_repack, then (first call) the handle's plan
+int repack_prepare(pnrf_mlp* h, const float* const* W, const float* const* b, const int* in_dim, const int* out_dim, int n_layers);
+
 }  // namespace pnrf
 
-// Packed, device-resident network (immutable after pnrf_mlp_pack).
+// Packed, device-resident network (weights rewritten in place by pnrf_mlp_repack only).
 struct pnrf_mlp {
   int net;               // PNRF_NET_*
   int prec;              // pnrf::PREC_*
@@ -80,6 +97,7 @@ struct pnrf_mlp {
   int device;
   int variant;           // PNRF_VARIANT_* (pnrf_mlp_set_variant); 0 = default kernels
   int shape;             // workgroup shape of the fused stages (pnrf_mlp_set_shape): PNRF_SHAPE_AUTO = per launch from the column count, or one forced
+  pnrf::RepackPlan* plan;   // NULL until the first pnrf_mlp_repack
 };
 
 // pnrf_sampler_fwd_ws with the caller's word that the workspace's counters are zero (a context's workspace): no memset on the stream

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "pnrf_common.h"
+#include "pnrf_pack_rules.h"
 
 namespace pnrf {
 
@@ -132,20 +133,10 @@ struct Image {
 };
 
 // ---- layers and fragments ---------------------------------------------------------------------------------------------
-// fp32 -> bf16, round to nearest even; NaN stays NaN.
-static uint16_t f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static uint16_t f2h(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-static float h2f(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-typedef uint16_t (*Round16)(float);
-
+// What an element of a stream IS — roundings, scalings, lane / row / feature indexing — is stated once, in pnrf_pack_rules.h, for this packer and for
+// the device repack kernels (pnrf_repack.hip).  Here: which layers a net's streams have, with which maps, at which slots.
 struct Layer {
-  const float* W;
-  const float* b;
+  PackSrc W, b;              // the caller's W[l] / b[l] (by index: a device plan outlives the pointers of one call) or a derived matrix (by address)
   int in_dim, out_dim;
   int nt;                    // output tiles (32x32x16: 32 rows; 16x16x32 and f32: 16 rows)
   int nk;                    // k-steps (32x32x16: 16 features each; 16x16x32: 32 each; f32: 4 each, a multiple of 4)
@@ -156,7 +147,11 @@ struct Layer {
   int x_from = 1 << 30;      // skip layer (mmnetskips): input columns >= x_from are the net input's (first-layer-like) and carry xscale instead of wscale
   double xscale = 1.0;
   int slot_align = 1;        // slots of the layer in a stream are rounded up to a multiple of this (skip layers: NSLOTS, pnrf_layout.h)
+  float bpost = 1.f;         // bias table entries times this, in fp32 (pass 1: a skip layer's accumulators run at scale 2^11)
 };
+static PackSrc src_w(int l, int off = 0) { return PackSrc{nullptr, l, off}; }
+static PackSrc src_b(int l) { return PackSrc{nullptr, PACK_MAX_LAYERS + l, 0}; }
+static PackSrc src_at(const float* p) { return PackSrc{p, -1, 0}; }
 // ELU nets on log2(e)-scaled activations: first layer W, every ELU layer's bias x log2(e); output layer W / log2(e).  The x-columns of a skip layer
 // multiply the unscaled net input like the first layer's and get the factor too; its h-columns multiply scaled activations and do not
 static void scale_for_elu(std::vector<Layer>& Ls) {
@@ -173,124 +168,96 @@ static size_t pair_slots(const Layer& L, int planes) { return frag_slots(L, (siz
 static size_t b16_slots(const Layer& L, int) { return pair_slots(L, 1); }
 static size_t h16x2_slots(const Layer& L, int) { return pair_slots(L, 2); }
 
-// weight (out, in) on the stream's scale, in double (0 for padding rows / columns)
-static inline double wdbl(const Layer& L, int out, int in) { return (out >= 0 && in >= 0) ? (double)L.W[(size_t)out * L.in_dim + in] * (in >= L.x_from ? L.xscale : L.wscale) : 0.0; }
-static inline float wval(const Layer& L, int out, int in) { return (float)wdbl(L, out, in); }
-// split fp16 of a value: hi, and the remainder times 2^11
-static inline void split_h16(double w, uint16_t* hi, uint16_t* lo) { *hi = f2h((float)w); *lo = f2h((float)((w - (double)h2f(*hi)) * H16_LO_SCALE)); }
-
-// 32x32x16 fragment of tile `to`: lane = (row r = lane & 31, half h = lane >> 5), 8 features of the k-step whose map is kmap[h * 8 + j]
-static void pack_frag_32(const Layer& L, int to, const int* kmap, Round16 rnd, float scale, uint16_t* frag) {
-  for (int lane = 0; lane < 64; ++lane) {
-    const int out = L.out_map[to * 32 + (lane & 31)];
-    for (int j = 0; j < 8; ++j) frag[lane * 8 + j] = rnd(wval(L, out, kmap[(lane >> 5) * 8 + j]) * scale);
+// Where a net's packed bytes go: into an image in host memory (plan == nullptr: the matrices of P are read here), or — the sections of `img` being a
+// handle's device buffers — into the tables of a device plan, which the repack kernels run on whatever matrices a call brings (P is never read)
+struct PlanBuild {
+  std::vector<PackEntry> entries;
+  std::vector<int> maps;
+  std::vector<RepackJob> jobs;
+  std::vector<DeriveOp> ops;
+  RepackPlan* plan;
+  hipError_t err = hipSuccess;
+};
+struct Sink {
+  const Image& img;
+  PackPtrs P;
+  PlanBuild* plan;
+  std::vector<std::vector<float>> own;
+  // a derived matrix of n floats, zero-filled: host memory, or device scratch owned by the plan
+  float* derived(size_t n) {
+    if (!plan) { own.emplace_back(n, 0.f); return own.back().data(); }
+    void* d = nullptr;
+    if (plan->err == hipSuccess) plan->err = hipMalloc(&d, n * sizeof(float));
+    if (d) { plan->plan->allocs.push_back(d); plan->plan->scratch.push_back({d, n * sizeof(float)}); }
+    return (float*)d;
   }
+};
+static PackLayer view(const Layer& L, const PackPtrs& P) {
+  return PackLayer{resolve(P, L.W), resolve(P, L.b), L.in_map.data(), L.out_map.data(), L.in_dim, L.nt, L.nk, L.x_from, L.wscale, L.bscale, L.xscale, L.bpost};
 }
-static void pack_layer_32(const Layer& L, Round16 rnd, char* dst) {
-  for (int to = 0; to < L.nt; ++to)
-    for (int ks = 0; ks < L.nk; ++ks) pack_frag_32(L, to, &L.in_map[ks * 16], rnd, 1.f, (uint16_t*)(dst + ((size_t)to * L.nk + ks) * FRAG_BYTES));
-}
-static void pack_layer_bf16(const Layer& L, int, char* dst) { pack_layer_32(L, f2bf, dst); }
-static void pack_layer_f16(const Layer& L, int, char* dst) { pack_layer_32(L, f2h, dst); }      // refine default; pass 1 of the two-pass sampler
-// 16x16x4: lane = (row i = lane&15, quarter q = lane>>4); a fragment = 4 consecutive k-steps
-static void pack_layer_f32(const Layer& L, int, char* dst) {
-  const int ks4 = L.nk / 4;
-  for (int to = 0; to < L.nt; ++to)
-    for (int fr = 0; fr < ks4; ++fr) {
-      float* frag = (float*)(dst + ((size_t)to * ks4 + fr) * FRAG_BYTES);
-      for (int lane = 0; lane < 64; ++lane) {
-        const int r = lane & 15, q = lane >> 4;
-        const int out = L.out_map[to * 16 + r];
-        for (int i = 0; i < 4; ++i) frag[lane * 4 + i] = wval(L, out, L.in_map[(4 * fr + i) * 4 + q]);
-      }
+static void pack_layer(const Layer& L, const PackPtrs& P, int kind, char* dst) {
+  const PackLayer v = view(L, P);
+  const int frags = pack_frags(kind, v);
+  for (int f = 0; f < frags; ++f)
+    for (int lane = 0; lane < 64; ++lane) {
+      PackLane o;
+      if (pack_lane(kind, v, f, lane, &o)) memcpy(dst + (size_t)f * FRAG_BYTES + lane * 16, &o, 16);
     }
 }
-
-// 16x16x32 (layer_b16 / layer_e16 / layer_h16x2): in_map [nk][4][8], out_map [nt][16], fragments (tile pair, ks, tile-in-pair, plane); rnd = nullptr:
-// split fp16, two planes hi / lo * 2^11 of the scaled value itself
-static void pack_layer_16(const Layer& L, Round16 rnd, char* dst) {
-  const int planes = rnd ? 1 : 2;
-  for (int tp = 0; tp < L.nt / 2; ++tp)
-    for (int ks = 0; ks < L.nk; ++ks)
-      for (int t = 0; t < 2; ++t) {
-        uint16_t* frag = (uint16_t*)(dst + (((size_t)tp * L.nk + ks) * 2 + t) * planes * FRAG_BYTES);
-        for (int lane = 0; lane < 64; ++lane) {
-          const int r = lane & 15, g = lane >> 4;
-          const int out = L.out_map[(2 * tp + t) * 16 + r];
-          for (int j = 0; j < 8; ++j) {
-            const int in = L.in_map[(ks * 4 + g) * 8 + j];
-            if (rnd) frag[lane * 8 + j] = rnd(wval(L, out, in));
-            else split_h16(wdbl(L, out, in), &frag[lane * 8 + j], &frag[FRAG_BYTES / 2 + lane * 8 + j]);
-          }
-        }
-      }
+static void plan_layer(PlanBuild& pb, const Layer& L, int kind, size_t dst_off) {
+  PackEntry e{L.W, L.b, (int)pb.maps.size(), 0, L.in_dim, L.nt, L.nk, L.x_from, L.wscale, L.bscale, L.xscale, L.bpost, kind, 0, (uint32_t)dst_off};
+  pb.maps.insert(pb.maps.end(), L.in_map.begin(), L.in_map.end());
+  e.out_map = (int)pb.maps.size();
+  pb.maps.insert(pb.maps.end(), L.out_map.begin(), L.out_map.end());
+  e.frags = pack_frags(kind, PackLayer{nullptr, nullptr, nullptr, nullptr, L.in_dim, L.nt, L.nk, L.x_from, 1.0, 1.0, 1.0, 1.f});
+  RepackJob& j = pb.jobs.back();
+  j.count++; j.max_frags = e.frags > j.max_frags ? e.frags : j.max_frags;
+  pb.entries.push_back(e);
 }
-static void pack_layer_b16(const Layer& L, int, char* dst) { pack_layer_16(L, f2bf, dst); }
-static void pack_layer_e16(const Layer& L, int, char* dst) { pack_layer_16(L, f2h, dst); }
-static void pack_layer_h16x2(const Layer& L, int, char* dst) { pack_layer_16(L, nullptr, dst); }
-
-// pass 1's split first layer (one k-step): per tile a W_hi fragment and a W_lo * 2^11 fragment.  xmap[h * 8 + j] = input column of the k-step
-static void pack_tile_f16x2(const Layer& L, int to, const int* xmap, uint16_t* hi, uint16_t* lo) {
-  for (int lane = 0; lane < 64; ++lane) {
-    const int out = L.out_map[to * 32 + (lane & 31)];
-    for (int j = 0; j < 8; ++j) split_h16(wdbl(L, out, xmap[(lane >> 5) * 8 + j]), &hi[lane * 8 + j], &lo[lane * 8 + j]);
-  }
-}
-static void pack_layer0_f16x2(const Layer& L, char* dst) {
-  for (int to = 0; to < L.nt; ++to)
-    pack_tile_f16x2(L, to, L.in_map.data(), (uint16_t*)(dst + ((size_t)to * 2 + 0) * FRAG_BYTES), (uint16_t*)(dst + ((size_t)to * 2 + 1) * FRAG_BYTES));
-}
-// ... and a skip layer of that stream (pnrf_layout.h, P1_KS_X): per tile the KS_HID plain fp16 fragments of the h-columns times 2^11, then of the x-columns
-// W_hi 2^11 and the first layer's pair W_hi, W_lo 2^11 (in_map = [KS_HID k-steps of the hidden layer | one k-step of x])
-static void pack_layer_f16_skip(const Layer& L, char* dst) {
-  const int kt = KS_HID + P1_KS_X;
-  for (int to = 0; to < L.nt; ++to) {
-    uint16_t* frag = (uint16_t*)(dst + (size_t)to * kt * FRAG_BYTES);
-    for (int ks = 0; ks < KS_HID; ++ks) pack_frag_32(L, to, &L.in_map[ks * 16], f2h, P1_SKIP_SCALE, frag + ks * (FRAG_BYTES / 2));
-    uint16_t *his = frag + KS_HID * (FRAG_BYTES / 2), *hi = his + FRAG_BYTES / 2;
-    pack_tile_f16x2(L, to, L.in_map.data() + KS_HID * 16, hi, hi + FRAG_BYTES / 2);
-    for (int i = 0; i < 64 * 8; ++i) his[i] = f2h(h2f(hi[i]) * P1_SKIP_SCALE);
-  }
-}
-
-static void pack_bias(const Layer& L, bool rows16, float* dst) {
-  if (rows16) {      // [tile][16 rows] in tile-row order: lane quarter q reads rows 4q..4q+3
-    for (int i = 0; i < L.nt * 16; ++i) dst[i] = L.out_map[i] >= 0 ? (float)((double)L.b[L.out_map[i]] * L.bscale) : 0.f;
-    return;
-  }
-  for (int to = 0; to < L.nt; ++to)      // 32-row tiles: [tile][half][16 registers]
-    for (int h = 0; h < 2; ++h)
-      for (int g = 0; g < 16; ++g) {
-        const int out = L.out_map[to * 32 + acc_row(g, h)];
-        dst[(to * 2 + h) * 16 + g] = out >= 0 ? (float)((double)L.b[out] * L.bscale) : 0.f;
-      }
-}
+static void run_derive(const DeriveOp& op, const PackPtrs& P);
+static void derive(Sink& sk, const DeriveOp& op) { if (sk.plan) sk.plan->ops.push_back(op); else run_derive(op, sk.P); }
 
 // ---- the internal layout checks: whatever is written into a section must be exactly as long as expected_counts() made it ------------------------
 // One weight stream: the layers' fragments, each layer at the slot where the one before it ends; the stream ends on a whole turn of the ring
-template <class Slots, class Pack>
-static int pack_stream(const std::vector<Layer>& Ls, const Image& img, int s, const char* what, Slots slots_of, Pack pack, size_t* used = nullptr) {
+template <class Slots, class Kind>
+static int pack_stream(const std::vector<Layer>& Ls, Sink& sk, int s, const char* what, Slots slots_of, Kind kind_of, size_t* used = nullptr) {
+  const Image& img = sk.img;
   size_t n = 0;
   for (size_t l = 0; l < Ls.size(); ++l) n += slots_of(Ls[l], (int)l);
   if (used) *used = n;
   PNRF_REQUIRE((size_t)pad_slots((int)n) * SLOT_BYTES == img.bytes[s], PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (%s stream: %d slots, kernels expect %zu)", what,
                pad_slots((int)n), img.bytes[s] / SLOT_BYTES);
   char* dst = (char*)img.sec[s];
-  for (size_t l = 0; l < Ls.size(); ++l) { pack(Ls[l], (int)l, dst); dst += slots_of(Ls[l], (int)l) * SLOT_BYTES; }
+  if (sk.plan) sk.plan->jobs.push_back(RepackJob{dst, (int)sk.plan->entries.size(), 0, 0});
+  size_t off = 0;
+  for (size_t l = 0; l < Ls.size(); ++l) {
+    if (sk.plan) plan_layer(*sk.plan, Ls[l], kind_of((int)l), off);
+    else pack_layer(Ls[l], sk.P, kind_of((int)l), dst + off);
+    off += slots_of(Ls[l], (int)l) * SLOT_BYTES;
+  }
   return 0;
 }
-static int pack_biases(const std::vector<Layer>& Ls, bool rows16, const Image& img, int s, const char* what) {
+static int pack_biases(const std::vector<Layer>& Ls, bool rows16, Sink& sk, int s, const char* what) {
+  const Image& img = sk.img;
   const int rows = rows16 ? 16 : 32;
   size_t n = 0;
   for (auto& L : Ls) n += (size_t)L.nt * rows;
   PNRF_REQUIRE(n * sizeof(float) == img.bytes[s], PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (%s bias table: %zu floats, kernels expect %zu)", what, n, img.bytes[s] / sizeof(float));
-  float* dst = (float*)img.sec[s];
-  for (auto& L : Ls) { pack_bias(L, rows16, dst); dst += (size_t)L.nt * rows; }
+  char* dst = (char*)img.sec[s];
+  if (sk.plan) sk.plan->jobs.push_back(RepackJob{dst, (int)sk.plan->entries.size(), 0, 0});
+  size_t off = 0;
+  for (auto& L : Ls) {
+    if (sk.plan) plan_layer(*sk.plan, L, rows16 ? PK_BIAS16 : PK_BIAS32, off);
+    else pack_layer(L, sk.P, rows16 ? PK_BIAS16 : PK_BIAS32, dst + off);
+    off += (size_t)L.nt * rows * sizeof(float);
+  }
   return 0;
 }
-static int put_map(const std::vector<int>& m, const Image& img, int s, const char* what) {
+// the weight-independent sections: written into an image, left alone in a handle that is repacked
+static int put_map(const std::vector<int>& m, Sink& sk, int s, const char* what) {
+  const Image& img = sk.img;
   PNRF_REQUIRE(m.size() * sizeof(int) == img.bytes[s], PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (%s map: %zu entries, kernels expect %zu)", what, m.size(), img.bytes[s] / sizeof(int));
-  if (!m.empty()) memcpy(img.sec[s], m.data(), img.bytes[s]);
+  if (!m.empty() && !sk.plan) memcpy(img.sec[s], m.data(), img.bytes[s]);
   return 0;
 }
 #define PNRF_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
@@ -338,13 +305,34 @@ static std::vector<int> half_order(const Layer& Z) {
   for (int to = 0; to < Z.nt; ++to) for (int h = 0; h < 2; ++h) for (int g = 0; g < 16; ++g) m[(to * 2 + h) * 16 + g] = Z.out_map[to * 32 + acc_row(g, h)];
   return m;
 }
-// fold n column groups of width 6 into one: dst[j] = sum_p row[6 p + j], fp64 sum rounded once.  The Pluecker 6-vectors of a ray's points are ONE vector in
-// exact arithmetic (pnrf_layout.h), so the weights that multiply them act as their sum
-static void fold6(const float* row, int n, float* dst) {
-  for (int j = 0; j < 6; ++j) {
-    double acc = 0.0;
-    for (int p = 0; p < n; ++p) acc += (double)row[6 * p + j];
-    dst[j] = (float)acc;
+// ---- derived matrices: the ops (DeriveKind, pnrf_pack_rules.h), and their host execution ----------------------------------------------------------
+static DeriveOp copy_op(float* dst, int ldd, PackSrc a, int lda, int rows, int cols) { return DeriveOp{DV_COPY, rows, cols, 0, dst, ldd, a, a, a, lda}; }
+// fold n column groups of width 6 into one: dst[r][j] = sum_p a[r][6 p + j]
+static DeriveOp fold6_op(float* dst, int ldd, PackSrc a, int lda, int rows, int n) { return DeriveOp{DV_FOLD6, rows, 6, n, dst, ldd, a, a, a, lda}; }
+static void run_derive(const DeriveOp& op, const PackPtrs& P) {
+  const float* A = resolve(P, op.a);
+  if (op.kind == DV_WC) {                      // derive_elem's sums, k outermost: each element still adds its products in ascending k
+    const float* B = resolve(P, op.b);
+    std::vector<double> acc(op.cols);
+    for (int r = 0; r < op.rows; ++r) {
+      for (int c = 0; c < op.cols; ++c) acc[c] = 0.0;
+      for (int k = 0; k < W_HID; ++k) {
+        const double wv = (double)A[(size_t)r * op.lda + k];
+        const float* row = B + (size_t)k * W_HID;
+        for (int c = 0; c < op.cols; ++c) acc[c] = mac_d(acc[c], wv, (double)row[c]);
+      }
+      for (int c = 0; c < op.cols; ++c) op.dst[(size_t)r * op.ldd + c] = (float)acc[c];
+    }
+  } else if (op.kind == DV_COLMAX) {
+    double cmax = 0.0;
+    for (int j = 0; j < W_HID; ++j) cmax = max_keep(colnorm(A, op.lda, j), cmax);
+    *op.dst = p1c_hidden(cmax);
+  } else if (op.kind == DV_OUTMAX) {
+    double mmax = 0.0;
+    for (int k = 0; k < 8; ++k) for (int j = 0; j < W_HID; ++j) mmax = max_keep(sq_d(A[(size_t)k * op.lda + j]), mmax);
+    *op.dst = p1c_out(mmax);
+  } else {
+    for (int e = 0, n = derive_elems(op); e < n; ++e) derive_elem(op, P, e);
   }
 }
 // the folded 6-vector as one k-step: group 0 supplies the 6 Pluecker features, the rest is padding (f32: two of four k-steps, one feature per quarter)
@@ -416,67 +404,63 @@ static int check_net(int net, Mats W, Mats b, const int* in_dim, const int* out_
 // The Linear layers of a sampler / refine / DoNeRFTRT stack as hidden layers of geometry G (first and last layer: the caller's).
 // Skip layers: W = [h-columns (256) | x-columns], the x-columns as the stream's first layer sees the input — the sampler's P ray points folded into one
 // Pluecker 6-vector, the refine net's as they are (kept in Wsk).  The hidden k-steps keep their maps; every stream appends its x k-steps
-static void base_layers(const Shape& s, Mats W, Mats b, const int* in_dim, const int* out_dim, const Geom& G, std::vector<std::vector<float>>& Wsk, std::vector<Layer>& Ls) {
+static void base_layers(Sink& sk, const Shape& s, const int* in_dim, const int* out_dim, const Geom& G, std::vector<Layer>& Ls) {
   const int xw = s.net == PNRF_NET_SAMPLER ? 6 : s.in0;
-  Ls.resize(s.n_layers); Wsk.resize(s.n_layers);
+  Ls.resize(s.n_layers);
   for (int l = 0; l < s.n_layers; ++l) {
     Layer& L = Ls[l];
-    L.W = W[l]; L.b = b[l]; L.in_dim = in_dim[l]; L.out_dim = out_dim[l];
+    L.W = src_w(l); L.b = src_b(l); L.in_dim = in_dim[l]; L.out_dim = out_dim[l];
     hidden_layer(L, G);
     if (!s.skip(l)) continue;
-    std::vector<float>& M = Wsk[l];
-    M.assign((size_t)W_HID * (W_HID + xw), 0.f);
-    for (int o = 0; o < W_HID; ++o) {
-      const float* row = W[l] + (size_t)o * (W_HID + s.in0);
-      float* dst = M.data() + (size_t)o * (W_HID + xw);
-      memcpy(dst, row + s.in0, W_HID * sizeof(float));
-      if (s.net == PNRF_NET_SAMPLER) fold6(row, s.npts, dst + W_HID);
-      else memcpy(dst + W_HID, row, s.in0 * sizeof(float));
-    }
-    L.W = M.data(); L.in_dim = W_HID + xw; L.x_from = W_HID; L.slot_align = NSLOTS;
+    const int ld = W_HID + xw, ldw = W_HID + s.in0;
+    float* M = sk.derived((size_t)W_HID * ld);
+    derive(sk, copy_op(M, ld, src_w(l, s.in0), ldw, W_HID, W_HID));
+    if (s.net == PNRF_NET_SAMPLER) derive(sk, fold6_op(M + W_HID, ld, src_w(l), ldw, W_HID, s.npts));
+    else derive(sk, copy_op(M + W_HID, ld, src_w(l), ldw, W_HID, s.in0));
+    L.W = src_at(M); L.in_dim = ld; L.x_from = W_HID; L.slot_align = NSLOTS;
   }
 }
 
-static int pack_sampler(const Shape& s, Mats W, Mats b, const int* in_dim, const int* out_dim, const Image& img) {
+static int pack_sampler(const Shape& s, const int* in_dim, const int* out_dim, Sink& sk) {
+  const Image& img = sk.img;
   const int n = s.n_layers;
   const bool full_stream = s.npts == S_NPTS && !s.skips;      // the sampler's unfolded stream (module-level forward, SAMPLER_F32_FULL): P = 48, no skips
-  std::vector<std::vector<float>> Wsk;
   std::vector<Layer> Ls;
-  base_layers(s, W, b, in_dim, out_dim, GF32, Wsk, Ls);
+  base_layers(sk, s, in_dim, out_dim, GF32, Ls);
   set_ksteps(Ls[0], GF32, S_KS0, [&](int kk, int q, int) { return full_stream ? sampler_in0(kk, q) : -1; });
   Layer& Z = Ls[n - 1];
   Z.nt = S_NT_LAST; Z.out_map.assign(16 * S_NT_LAST, -1);
   for (int tt = 0; tt < S_NT_LAST; ++tt) for (int q = 0; q < 4; ++q) for (int r = 0; r < 4; ++r) Z.out_map[tt * 16 + 4 * q + r] = sampler_out(tt, q, r);
-  PNRF_TRY(put_map(Ls[0].in_map, img, SEC_d_in0, "sampler input"));
-  PNRF_TRY(put_map(Z.out_map, img, SEC_d_out, "sampler output"));      // [tile][16 rows]: lane quarter q, reg r -> [tile*16 + 4q + r]
-  PNRF_TRY(pack_biases(Ls, true, img, SEC_d_bias, "sampler"));
+  PNRF_TRY(put_map(Ls[0].in_map, sk, SEC_d_in0, "sampler input"));
+  PNRF_TRY(put_map(Z.out_map, sk, SEC_d_out, "sampler output"));      // [tile][16 rows]: lane quarter q, reg r -> [tile*16 + 4q + r]
+  PNRF_TRY(pack_biases(Ls, true, sk, SEC_d_bias, "sampler"));
   PNRF_REQUIRE(img.bytes[SEC_d_tvals] == (full_stream ? S_NPTS * sizeof(float) : 0), PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (ray points)");
   if (full_stream) {
-    PNRF_TRY(pack_stream(Ls, img, SEC_d_blob, "unfolded sampler", f32_slots, pack_layer_f32));
-    pnrf_linspace(0.f, 1.f, S_NPTS, (float*)img.sec[SEC_d_tvals]);
+    PNRF_TRY(pack_stream(Ls, sk, SEC_d_blob, "unfolded sampler", f32_slots, [](int) { return PK_F32; }));
+    if (!sk.plan) pnrf_linspace(0.f, 1.f, S_NPTS, (float*)img.sec[SEC_d_tvals]);
   } else {
     PNRF_REQUIRE(img.bytes[SEC_d_blob] == 0, PNRF_E_SHAPE, "pnrf_mlp_pack: internal layout mismatch (unfolded stream of a sampler that has none)");
   }
 
   // every other stream has the folded first layer Wf[256x6] = sum_p W0[:, 6p:6p+6], and the folded input's k-step(s) behind the hidden ones of a skip layer
-  std::vector<float> wfold((size_t)W_HID * 6);
-  for (int o = 0; o < W_HID; ++o) fold6(W[0] + (size_t)o * s.in0, s.npts, &wfold[(size_t)o * 6]);
+  float* wfold = sk.derived((size_t)W_HID * 6);
+  derive(sk, fold6_op(wfold, 6, src_w(0), s.in0, W_HID, s.npts));
   auto fold_first = [&](std::vector<Layer>& Lx, const Geom& G, int nk, int (*feat)(int, int, int)) {
-    Lx[0].W = wfold.data(); Lx[0].in_dim = 6;
+    Lx[0].W = src_at(wfold); Lx[0].in_dim = 6;
     set_ksteps(Lx[0], G, nk, feat);
     for (int l = 1; l < n - 1; ++l) if (s.skip(l)) add_ksteps(Lx[l], G, nk, feat, W_HID);
   };
   // second stream: exact fp32.  K = 6 padded to 16 = one fragment per tile
   std::vector<Layer> Lf = Ls;
   fold_first(Lf, GF32, 4 * SF_KS4_0, folded_in_f32);
-  PNRF_TRY(pack_stream(Lf, img, SEC_d_blob_fold, "folded sampler", f32_slots, pack_layer_f32));
+  PNRF_TRY(pack_stream(Lf, sk, SEC_d_blob_fold, "folded sampler", f32_slots, [](int) { return PK_F32; }));
 
   // third stream: split fp16 (hi / lo*2^11) for layer_h16x2, hidden geometry of the 16x16x32 engine
   std::vector<Layer> Lh = Ls;
   scale_for_elu(Lh);                                         // weights only: this stream's kernel scales the shared bias table itself
   for (auto& L : Lh) hidden_inputs(L, G16);
   fold_first(Lh, G16, 1, folded_in);
-  PNRF_TRY(pack_stream(Lh, img, SEC_d_blob_h16, "split-fp16 sampler", h16x2_slots, pack_layer_h16x2));
+  PNRF_TRY(pack_stream(Lh, sk, SEC_d_blob_h16, "split-fp16 sampler", h16x2_slots, [](int) { return PK_H16X2; }));
 
   // fourth stream = pass 1 of the two-pass scheme (sampler_p1_kernel): plain fp16 on the 32x32x16 engine, folded first layer in
   // split fp16; its own bias table in that engine's [tile][half][16] order, log2(e)-scaled for the ELU layers; and the constants of the
@@ -484,42 +468,31 @@ static int pack_sampler(const Shape& s, Mats W, Mats b, const int* in_dim, const
   std::vector<Layer> Lp = Ls;
   scale_for_elu(Lp);
   for (auto& L : Lp) hidden_layer(L, G32);
-  fold_first(Lp, G32, 1, folded_in);                         // a skip layer's in_map = [16 hidden k-steps | the folded input's k-step]; fragments: pack_layer_f16_skip
+  fold_first(Lp, G32, 1, folded_in);                         // a skip layer's in_map = [16 hidden k-steps | the folded input's k-step]; fragments: PK_F16_SKIP
   Layer& Y = Lp[n - 1];
   Y.nt = 1; Y.out_map.assign(32, -1);
   for (int hh = 0; hh < 2; ++hh) for (int g = 0; g < 16; ++g) Y.out_map[acc_row(g, hh)] = sampler_p1_out(g, hh);
   size_t used = 0;
-  PNRF_TRY(pack_stream(Lp, img, SEC_d_blob_p1, "pass-1 sampler",
+  PNRF_TRY(pack_stream(Lp, sk, SEC_d_blob_p1, "pass-1 sampler",
                        [&](const Layer& L, int l) { return l == 0 ? (size_t)P1_SLOTS_L0 : s.skip(l) ? (size_t)P1_SLOTS_SKIP : tile_slots(L, l); },
-                       [&](const Layer& L, int l, char* dst) { if (l == 0) pack_layer0_f16x2(L, dst); else if (s.skip(l)) pack_layer_f16_skip(L, dst); else pack_layer_f16(L, l, dst); },
-                       &used));
+                       [&](int l) { return l == 0 ? PK_L0_F16X2 : s.skip(l) ? PK_F16_SKIP : PK_F16_32; }, &used));
   PNRF_REQUIRE(used == (size_t)p1_slots_used(s.nhid, s.skips) && img.bytes[SEC_d_p1c] == p1_nconst(s.nhid) * sizeof(float), PNRF_E_SHAPE,
                "pnrf_mlp_pack: internal layout mismatch (pass-1 stream uses %zu slots, %zu constants)", used, img.bytes[SEC_d_p1c] / sizeof(float));
-  PNRF_TRY(pack_biases(Lp, false, img, SEC_d_bias_p1, "pass-1"));
-  float* bias_p1 = (float*)img.sec[SEC_d_bias_p1];
-  for (int l = 1; l < n - 1; ++l)
-    if (s.skip(l)) for (int i = 0; i < W_HID; ++i) bias_p1[l * W_HID + i] *= P1_SKIP_SCALE;      // the skip layer's accumulators run at scale 2^11
+  for (int l = 1; l < n - 1; ++l) if (s.skip(l)) Lp[l].bpost = P1_SKIP_SCALE;      // the skip layer's accumulators run at scale 2^11
+  PNRF_TRY(pack_biases(Lp, false, sk, SEC_d_bias_p1, "pass-1"));
   float* p1c = (float*)img.sec[SEC_d_p1c];      // [0] output-layer constant, [1 + l] C of hidden layer l (sampler_p1_kernel)
-  for (int l = 1; l <= s.nhid; ++l) {                             // C_l = max over input features j of the column norm sum_i W_l[i,j]^2 — of a skip layer over
-    double cmax = 0.0;                                          // its h-columns only: the x-part is formed split-accurate like layer 0
-    for (int j = 0; j < W_HID; ++j) {
-      double cn = 0.0;
-      for (int i = 0; i < W_HID; ++i) { const double w = (double)Ls[l].W[(size_t)i * Ls[l].in_dim + j]; cn += w * w; }
-      cmax = cn > cmax ? cn : cmax;
-    }
-    p1c[l] = (float)(cmax * (1.0 + 1e-6));
-  }
-  double mmax = 0.0;                                              // depth rows of the output layer
-  for (int k = 0; k < 8; ++k) for (int j = 0; j < W_HID; ++j) { const double w = (double)W[n - 1][(size_t)k * W_HID + j]; mmax = w * w > mmax ? w * w : mmax; }
-  p1c[0] = (float)(mmax / (LOG2E_D * LOG2E_D) * (1.0 + 1e-6));
+  // C_l = max over input features j of the column norm sum_i W_l[i,j]^2 — of a skip layer over its h-columns only (they lie behind the x-columns in the
+  // caller's matrix): the x-part is formed split-accurate like layer 0
+  for (int l = 1; l <= s.nhid; ++l)
+    derive(sk, DeriveOp{DV_COLMAX, 0, 0, 0, p1c + l, 0, src_w(l, s.skip(l) ? s.in0 : 0), src_w(l), src_w(l), in_dim[l]});
+  derive(sk, DeriveOp{DV_OUTMAX, 0, 0, 0, p1c, 0, src_w(n - 1), src_w(n - 1), src_w(n - 1), W_HID});      // depth rows of the output layer
   return 0;
 }
 
-static int pack_refine(const Shape& s, Mats W, Mats b, const int* in_dim, const int* out_dim, const Image& img) {
+static int pack_refine(const Shape& s, const int* in_dim, const int* out_dim, Sink& sk) {
   const int n = s.n_layers, nbv = s.nb, nv = refine_nv(nbv);
-  std::vector<std::vector<float>> Wsk;
   std::vector<Layer> Ls;
-  base_layers(s, W, b, in_dim, out_dim, G32, Wsk, Ls);
+  base_layers(sk, s, in_dim, out_dim, G32, Ls);
   scale_for_elu(Ls);          // every refine kernel computes its ELU on the log2(e) scale
   auto in0 = [&](int ks, int h, int j) { return refine_in0_nv(nv, nbv, ks, h, j); };
   set_ksteps(Ls[0], G32, 3 * nv + 3, in0);
@@ -530,31 +503,29 @@ static int pack_refine(const Shape& s, Mats W, Mats b, const int* in_dim, const 
     Z.out_map[acc_row(g, h)] = refine_out0(g, h);
     Z.out_map[32 + acc_row(g, h)] = refine_out1(g, h);
   }
-  PNRF_TRY(put_map(Ls[0].in_map, img, SEC_d_in0, "refine input"));
-  PNRF_TRY(put_map(half_order(Z), img, SEC_d_out, "refine output"));
-  PNRF_TRY(pack_stream(Ls, img, SEC_d_blob, "refine bf16", tile_slots, pack_layer_bf16));      // PNRF_VARIANT_BF16
-  PNRF_TRY(pack_stream(Ls, img, SEC_d_blob_f16, "refine fp16", tile_slots, pack_layer_f16));   // the same stream with fp16 operands: default of the refine stage
-  PNRF_TRY(pack_biases(Ls, false, img, SEC_d_bias, "refine"));
+  PNRF_TRY(put_map(Ls[0].in_map, sk, SEC_d_in0, "refine input"));
+  PNRF_TRY(put_map(half_order(Z), sk, SEC_d_out, "refine output"));
+  PNRF_TRY(pack_stream(Ls, sk, SEC_d_blob, "refine bf16", tile_slots, [](int) { return PK_BF16_32; }));      // PNRF_VARIANT_BF16
+  PNRF_TRY(pack_stream(Ls, sk, SEC_d_blob_f16, "refine fp16", tile_slots, [](int) { return PK_F16_32; }));   // the same stream with fp16 operands: default of the refine stage
+  PNRF_TRY(pack_biases(Ls, false, sk, SEC_d_bias, "refine"));
   if (s.skips) return 0;          // (PNRF_VARIANT_REFINE_16X16 does not take skip nets)
 
   // the streams of the 16x16x32 engine (layer_e16 / refine16_kernel; fp16 operands, log2(e)-scaled like every refine stream) and their bias table:
   // the full first layer for rows from memory, and for the projecting head the first layer with the eight Pluecker 6-vectors folded into one
   const int nv4 = refine16_nv(nbv), fin = 6 + 24 * nbv;
-  std::vector<float> wfold((size_t)W_HID * fin);
-  for (int o = 0; o < W_HID; ++o) {
-    fold6(W[0] + (size_t)o * s.in0, 8, &wfold[(size_t)o * fin]);
-    memcpy(&wfold[(size_t)o * fin + 6], W[0] + (size_t)o * s.in0 + 48, 24 * nbv * sizeof(float));
-  }
+  float* wfold = sk.derived((size_t)W_HID * fin);
+  derive(sk, fold6_op(wfold, fin, src_w(0), s.in0, W_HID, 8));
+  derive(sk, copy_op(wfold + 6, fin, src_w(0, 48), s.in0, W_HID, 24 * nbv));
   for (int fold = 0; fold < 2; ++fold) {
     std::vector<Layer> Lr = Ls;
     for (auto& L : Lr) hidden_layer(L, G16);
-    if (fold) { Lr[0].W = wfold.data(); Lr[0].in_dim = fin; }
+    if (fold) { Lr[0].W = src_at(wfold); Lr[0].in_dim = fin; }
     set_ksteps(Lr[0], G16, refine16_ks0(nv4, fold != 0), [&](int ks, int g, int j) { return refine16_in0(nv4, nbv, ks, g, j, fold != 0); });
     Layer& Y = Lr[n - 1];
     Y.nt = 2 * R16_NTP_LAST; Y.out_map.assign(16 * Y.nt, -1);
     for (int T = 0; T < Y.nt; ++T) for (int r16 = 0; r16 < 16; ++r16) Y.out_map[T * 16 + r16] = refine16_out(T, r16);
-    PNRF_TRY(pack_stream(Lr, img, fold ? SEC_d_blob_fold : SEC_d_blob_b16, fold ? "refine 16x16 folded" : "refine 16x16", b16_slots, pack_layer_e16));
-    if (!fold) PNRF_TRY(pack_biases(Lr, true, img, SEC_d_bias_b16, "refine 16x16"));
+    PNRF_TRY(pack_stream(Lr, sk, fold ? SEC_d_blob_fold : SEC_d_blob_b16, fold ? "refine 16x16 folded" : "refine 16x16", b16_slots, [](int) { return PK_E16; }));
+    if (!fold) PNRF_TRY(pack_biases(Lr, true, sk, SEC_d_bias_b16, "refine 16x16"));
   }
   return 0;
 }
@@ -562,12 +533,11 @@ static int pack_refine(const Shape& s, Mats W, Mats b, const int* in_dim, const 
 // the view embedding's one k-step on the 16x16x32 engine
 static int nerf16_view_in(int, int g, int j) { return nerf16_inx(g, j); }
 
-static int pack_nerf(const Shape& s, Mats W, Mats b, const int* in_dim, const int* out_dim, const Image& img) {
+static int pack_nerf(const Shape& s, const int* in_dim, const int* out_dim, Sink& sk) {
   const int n = s.n_layers;
-  std::vector<std::vector<float>> Wsk;
   std::vector<Layer> Ls, Lb;
   std::vector<int> inx_map;
-  base_layers(s, W, b, in_dim, out_dim, G32, Wsk, Ls);
+  base_layers(sk, s, in_dim, out_dim, G32, Ls);
   Lb = Ls;
   set_ksteps(Ls[0], G32, N_KS0, nerf_in0);
   Layer& Z = Ls[n - 1];
@@ -575,61 +545,48 @@ static int pack_nerf(const Shape& s, Mats W, Mats b, const int* in_dim, const in
   append_ksteps(inx_map, G32, N_KSX, nerf_inx);
   Z.nt = 1; Z.out_map.assign(32, -1);
   for (int h = 0; h < 2; ++h) for (int g = 0; g < 16; ++g) Z.out_map[acc_row(g, h)] = nerf_out(g, h);
-  PNRF_TRY(put_map(Ls[0].in_map, img, SEC_d_in0, "NeRF input"));
-  PNRF_TRY(put_map(inx_map, img, SEC_d_inx, "NeRF view input"));
-  PNRF_TRY(put_map(half_order(Z), img, SEC_d_out, "NeRF output"));
-  PNRF_TRY(pack_stream(Ls, img, SEC_d_blob, "NeRF 32x32", tile_slots, pack_layer_bf16));
-  PNRF_TRY(pack_biases(Ls, false, img, SEC_d_bias, "NeRF 32x32"));
+  PNRF_TRY(put_map(Ls[0].in_map, sk, SEC_d_in0, "NeRF input"));
+  PNRF_TRY(put_map(inx_map, sk, SEC_d_inx, "NeRF view input"));
+  PNRF_TRY(put_map(half_order(Z), sk, SEC_d_out, "NeRF output"));
+  PNRF_TRY(pack_stream(Ls, sk, SEC_d_blob, "NeRF 32x32", tile_slots, [](int) { return PK_BF16_32; }));
+  PNRF_TRY(pack_biases(Ls, false, sk, SEC_d_bias, "NeRF 32x32"));
   // second stream for the 16x16x32 engine (layer_b16): 16-row tiles in pairs, 32-deep k-steps; with bf16 and with fp16 operands (the default of the NeRF stage)
   for (auto& L : Lb) hidden_layer(L, G16);
   set_ksteps(Lb[0], G16, NB_KS0, nerf16_in0);
   add_ksteps(Lb[n - 1], G16, 1, nerf16_view_in, W_HID);
   first_rows_out(Lb[n - 1], G16, 2, N_OUT);                             // rows 0..3 of tile 0 = rgb, sigma; tile 1 is padding
-  PNRF_TRY(pack_stream(Lb, img, SEC_d_blob_b16, "NeRF bf16", b16_slots, pack_layer_b16));
-  PNRF_TRY(pack_stream(Lb, img, SEC_d_blob_f16, "NeRF fp16", b16_slots, pack_layer_e16));
-  return pack_biases(Lb, true, img, SEC_d_bias_b16, "NeRF 16x16");     // [tile][16 rows]
+  PNRF_TRY(pack_stream(Lb, sk, SEC_d_blob_b16, "NeRF bf16", b16_slots, [](int) { return PK_B16; }));
+  PNRF_TRY(pack_stream(Lb, sk, SEC_d_blob_f16, "NeRF fp16", b16_slots, [](int) { return PK_E16; }));
+  return pack_biases(Lb, true, sk, SEC_d_bias_b16, "NeRF 16x16");     // [tile][16 rows]
 }
 
 // NeRF-class fine net: 12 Linear modules -> 10 engine layers (feature_linear is folded into the views layer, which shares its layer with alpha).
-static int pack_nerfcls(Mats W, Mats b, const int* in_dim, const int* out_dim, const Image& img) {
+static int pack_nerfcls(const int* in_dim, const int* out_dim, Sink& sk) {
   // E89: views layer with feature_linear folded in (helpers:842-848; see pnrf_layout.h) + alpha as row 128.
   //   rows 0..127: Wc[r, :256] = sum_k Wv[r, k] Wf[k, :]  (fp64), Wc[r, 256:283] = Wv[r, 256:283], bc[r] = bv[r] + sum_k Wv[r, k] bf[k]
   //   row 128    : Wc[128, :256] = Wa, no view inputs, bc[128] = ba
   const int VI = W_HID + N_INV, VO = W_HID / 2;
-  std::vector<float> Wc((size_t)(VO + 1) * VI, 0.f), bc(VO + 1, 0.f);
-  {
-    const float *Wf = W[8], *bf = b[8], *Wa = W[9], *Wv = W[10], *bv = b[10];
-    std::vector<double> acc(W_HID);
-    for (int r = 0; r < VO; ++r) {
-      for (int c = 0; c < W_HID; ++c) acc[c] = 0.0;
-      double ab = (double)bv[r];
-      for (int k = 0; k < W_HID; ++k) {
-        const double wv = (double)Wv[(size_t)r * VI + k];
-        const float* row = Wf + (size_t)k * W_HID;
-        for (int c = 0; c < W_HID; ++c) acc[c] += wv * (double)row[c];
-        ab += wv * (double)bf[k];
-      }
-      for (int c = 0; c < W_HID; ++c) Wc[(size_t)r * VI + c] = (float)acc[c];
-      for (int c = 0; c < N_INV; ++c) Wc[(size_t)r * VI + W_HID + c] = Wv[(size_t)r * VI + W_HID + c];
-      bc[r] = (float)ab;
-    }
-    for (int c = 0; c < W_HID; ++c) Wc[(size_t)VO * VI + c] = Wa[c];
-    bc[VO] = b[9][0];
-  }
+  float* Wc = sk.derived((size_t)(VO + 1) * VI);
+  float* bc = sk.derived(VO + 1);
+  derive(sk, DeriveOp{DV_WC, VO, W_HID, 0, Wc, VI, src_w(10), src_w(8), src_b(10), VI});
+  derive(sk, DeriveOp{DV_BC, VO, 1, 0, bc, 1, src_w(10), src_b(8), src_b(10), VI});
+  derive(sk, copy_op(Wc + W_HID, VI, src_w(10, W_HID), VI, VO, N_INV));
+  derive(sk, copy_op(Wc + (size_t)VO * VI, VI, src_w(9), W_HID, 1, W_HID));
+  derive(sk, copy_op(bc + VO, 1, src_b(9), 1, 1, 1));
   // the ten engine layers on one geometry: E0..E7 = pts0..7, E89, E10 = rgb (helpers:850)
   auto layers = [&](const Geom& G, int ks0, int (*in0)(int, int, int), int ksx, int (*inx)(int, int, int), int ks10) {
     std::vector<Layer> Ls(10);
     for (int e = 0; e < 10; ++e) {
       const int lin = e < 8 ? e : 11;
       Layer& L = Ls[e];
-      L.W = W[lin]; L.b = b[lin]; L.in_dim = in_dim[lin]; L.out_dim = out_dim[lin];
+      L.W = src_w(lin); L.b = src_b(lin); L.in_dim = in_dim[lin]; L.out_dim = out_dim[lin];
       hidden_layer(L, G);
     }
     set_ksteps(Ls[0], G, ks0, in0);               // E0: positional k-steps (same slot order as the DoNeRFTRT first layer)
     hidden_inputs(Ls[5], G, N_IN);                // E5: input = cat[pts(63), h(256)] (helpers:838-839): the hidden k-steps on columns 63.., then the positional k-steps on columns 0..62
     add_ksteps(Ls[5], G, ks0, in0);
     Layer& E89 = Ls[8];
-    E89.W = Wc.data(); E89.b = bc.data(); E89.in_dim = VI; E89.out_dim = VO + 1;
+    E89.W = src_at(Wc); E89.b = src_at(bc); E89.in_dim = VI; E89.out_dim = VO + 1;
     add_ksteps(E89, G, ksx, inx, W_HID);
     first_rows_out(E89, G, 5 * 32 / G.tile_rows, VO + 1);      // rows 0..127 = view layer, alpha = output 128 -> the first row of a tile of its own
     set_ksteps(Ls[9], G, ks10, G.hidden);         // 128 inputs
@@ -640,17 +597,29 @@ static int pack_nerfcls(Mats W, Mats b, const int* in_dim, const int* out_dim, c
   for (int g = 0; g < 3; ++g) Ls[9].out_map[acc_row(g, 0)] = g;
   std::vector<int> inx_map;
   append_ksteps(inx_map, G32, N_KSX, nerf_inx);
-  PNRF_TRY(put_map(Ls[0].in_map, img, SEC_d_in0, "NeRF-class input"));
-  PNRF_TRY(put_map(inx_map, img, SEC_d_inx, "NeRF-class view input"));
-  PNRF_TRY(put_map(std::vector<int>(64, -1), img, SEC_d_out, "NeRF-class output"));      // module-level store map, rgb only (alpha handled by the kernel)
-  PNRF_TRY(pack_stream(Ls, img, SEC_d_blob, "NeRF-class 32x32", tile_slots, pack_layer_bf16));
-  PNRF_TRY(pack_biases(Ls, false, img, SEC_d_bias, "NeRF-class 32x32"));
+  PNRF_TRY(put_map(Ls[0].in_map, sk, SEC_d_in0, "NeRF-class input"));
+  PNRF_TRY(put_map(inx_map, sk, SEC_d_inx, "NeRF-class view input"));
+  PNRF_TRY(put_map(std::vector<int>(64, -1), sk, SEC_d_out, "NeRF-class output"));      // module-level store map, rgb only (alpha handled by the kernel)
+  PNRF_TRY(pack_stream(Ls, sk, SEC_d_blob, "NeRF-class 32x32", tile_slots, [](int) { return PK_BF16_32; }));
+  PNRF_TRY(pack_biases(Ls, false, sk, SEC_d_bias, "NeRF-class 32x32"));
   // second stream for the 16x16x32 engine (nerf16_kernel<true>): same ten engine layers, 16-row tiles in pairs, 32-deep k-steps, with bf16 / fp16 operands
   std::vector<Layer> Lb = layers(G16, NB_KS0, nerf16_in0, 1, nerf16_view_in, CB_KS10);
   first_rows_out(Lb[9], G16, 2, 3);
-  PNRF_TRY(pack_stream(Lb, img, SEC_d_blob_b16, "NeRF-class bf16", b16_slots, pack_layer_b16));
-  PNRF_TRY(pack_stream(Lb, img, SEC_d_blob_f16, "NeRF-class fp16", b16_slots, pack_layer_e16));
-  return pack_biases(Lb, true, img, SEC_d_bias_b16, "NeRF-class 16x16");
+  PNRF_TRY(pack_stream(Lb, sk, SEC_d_blob_b16, "NeRF-class bf16", b16_slots, [](int) { return PK_B16; }));
+  PNRF_TRY(pack_stream(Lb, sk, SEC_d_blob_f16, "NeRF-class fp16", b16_slots, [](int) { return PK_E16; }));
+  return pack_biases(Lb, true, sk, SEC_d_bias_b16, "NeRF-class 16x16");
+}
+
+static PackPtrs ptrs_of(Mats W, Mats b, int n_layers) {
+  PackPtrs P{};
+  for (int l = 0; l < n_layers && l < PACK_MAX_LAYERS; ++l) { P.m[l] = W[l]; P.m[PACK_MAX_LAYERS + l] = b[l]; }
+  return P;
+}
+static int pack_net(const Shape& s, const int* in_dim, const int* out_dim, Sink& sk) {
+  return s.net == PNRF_NET_SAMPLER  ? pack_sampler(s, in_dim, out_dim, sk)
+         : s.net == PNRF_NET_REFINE ? pack_refine(s, in_dim, out_dim, sk)
+         : s.net == PNRF_NET_NERF   ? pack_nerf(s, in_dim, out_dim, sk)
+                                    : pack_nerfcls(in_dim, out_dim, sk);
 }
 
 // Checks, then the image: header from expected_counts(), zero-filled sections, the net kind's packer.  own: pack into this vector (pnrf_mlp_pack: no
@@ -675,13 +644,69 @@ static int pack_image(int net, Mats W, Mats b, const int* in_dim, const int* out
   }
   uint8_t* p = (uint8_t*)buf + sizeof(EngineHeader);
   for (int i = 0; i < ENGINE_SECTIONS; ++i) { img.sec[i] = p; p += img.bytes[i]; }
-  PNRF_TRY(net == PNRF_NET_SAMPLER  ? pack_sampler(s, W, b, in_dim, out_dim, img)
-           : net == PNRF_NET_REFINE ? pack_refine(s, W, b, in_dim, out_dim, img)
-           : net == PNRF_NET_NERF   ? pack_nerf(s, W, b, in_dim, out_dim, img)
-                                    : pack_nerfcls(W, b, in_dim, out_dim, img));
+  Sink sk{img, ptrs_of(W, b, n_layers), nullptr, {}};
+  PNRF_TRY(pack_net(s, in_dim, out_dim, sk));
   img.hd.payload_bytes = payload;
   if (!own) img.hd.checksum = fnv1a((const uint8_t*)buf + sizeof(EngineHeader), payload);
   memcpy(buf, &img.hd, sizeof(img.hd));
+  return 0;
+}
+
+// ---- the device plan of a handle (pnrf_mlp_repack) ----------------------------------------------------------------------------------------------
+// The nets' packers above, run with the handle's device buffers as the image's sections: they record the streams' and bias tables' layer tables and the
+// derive ops instead of packing; the tables and the scratch of the derived matrices go to the device once.
+static void free_plan(RepackPlan* p) {
+  if (!p) return;
+  for (void* d : p->allocs) (void)hipFree(d);
+  delete p;
+}
+static const char* shape_text(char* buf, size_t n, int net, int nhid, int npts, int nb, uint32_t skips) {
+  snprintf(buf, n, "net kind %d, %d hidden layers, %d ray points, %d neighbour views, skip mask %08x", net, nhid, npts, nb, skips);
+  return buf;
+}
+int repack_prepare(pnrf_mlp* h, Mats W, Mats b, const int* in_dim, const int* out_dim, int n_layers) {
+  Shape s;
+  PNRF_TRY(check_net(h->net, W, b, in_dim, out_dim, n_layers, &s));
+  char t0[160], t1[160];
+  PNRF_REQUIRE(s.nhid == h->nhid && s.npts == h->npts && s.nb == h->nb && s.skips == h->skips, PNRF_E_SHAPE, "pnrf_mlp_repack: the weights are of another shape (%s) than the handle (%s)",
+               shape_text(t0, sizeof(t0), s.net, s.nhid, s.npts, s.nb, s.skips), shape_text(t1, sizeof(t1), h->net, h->nhid, h->npts, h->nb, h->skips));
+  int dev = -1;
+  PNRF_HIP(hipGetDevice(&dev));
+  PNRF_REQUIRE(dev == h->device, PNRF_E_STATE, "pnrf_mlp_repack: the handle lives on device %d, the current device is %d", h->device, dev);
+  pnrf_mlp want;
+  expected_counts(h->net, s.nhid, s.nb, s.npts, s.skips, &want);
+  Image img;
+  Section sec[ENGINE_SECTIONS], wsec[ENGINE_SECTIONS];
+  sections(h, sec);
+  sections(&want, wsec);
+  for (int i = 0; i < ENGINE_SECTIONS; ++i) {
+    PNRF_REQUIRE(sec[i].bytes == wsec[i].bytes && (sec[i].bytes == 0) == (*sec[i].dptr == nullptr), PNRF_E_STATE, "pnrf_mlp_repack: inconsistent handle (section %d)", i);
+    img.sec[i] = (uint8_t*)*sec[i].dptr; img.bytes[i] = sec[i].bytes;
+  }
+  if (h->plan) return 0;
+  RepackPlan* plan = new RepackPlan();
+  PlanBuild pb;
+  pb.plan = plan;
+  Sink sk{img, ptrs_of(W, b, n_layers), &pb, {}};
+  int rc = pack_net(s, in_dim, out_dim, sk);
+  hipError_t e = pb.err;
+  auto up = [&](const void* src, size_t bytes, void** dst) {
+    if (rc || e != hipSuccess || !bytes) return;
+    e = hipMalloc(dst, bytes);
+    if (e != hipSuccess) return;
+    plan->allocs.push_back(*dst);
+    e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+  };
+  up(pb.entries.data(), pb.entries.size() * sizeof(PackEntry), (void**)&plan->d_entries);
+  up(pb.maps.data(), pb.maps.size() * sizeof(int), (void**)&plan->d_maps);
+  up(pb.ops.data(), pb.ops.size() * sizeof(DeriveOp), (void**)&plan->d_ops);
+  if (!rc && e != hipSuccess) { set_error("pnrf_mlp_repack: device allocation/copy of the plan failed: %s", hipGetErrorString(e)); rc = (int)e; }
+  if (rc) { free_plan(plan); return rc; }
+  plan->jobs = pb.jobs;
+  plan->n_ops = (int)pb.ops.size();
+  for (auto& op : pb.ops) plan->max_elems = derive_elems(op) > plan->max_elems ? derive_elems(op) : plan->max_elems;
+  plan->fresh = true;
+  h->plan = plan;
   return 0;
 }
 
@@ -751,6 +776,7 @@ extern "C" int pnrf_mlp_free(pnrf_mlp_t* h) {
   sections(h, sec);
   for (int i = 0; i < ENGINE_SECTIONS; ++i)
     if (*sec[i].dptr) (void)hipFree(*sec[i].dptr);
+  free_plan(h->plan);
   delete h;
   return 0;
 }

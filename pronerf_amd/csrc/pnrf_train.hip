@@ -1896,6 +1896,30 @@ extern "C" int pnrf_trainer_flat(pnrf_trainer_t* t, int kind, float** ptr, int64
   return 0;
 }
 
+// Trainer -> packed handles on the device (pnrf_mlp_repack of each from the flat parameter array).  Reads t->P only: no close_split, no stale flags
+extern "C" int pnrf_trainer_publish(const pnrf_trainer_t* t, pnrf_mlp_t* sampler, pnrf_mlp_t* refine, pnrf_mlp_t* fine, void* stream) {
+  PNRF_REQUIRE(t, PNRF_E_ARG, "pnrf_trainer_publish: null trainer");
+  struct Net { pnrf_mlp_t* h; int first, count, kind; const char* name; };
+  const Net nets[3] = {{sampler, L_S, L_R - L_S, PNRF_NET_SAMPLER, "sampler"}, {refine, L_R, L_N - L_R, PNRF_NET_REFINE, "refine"}, {fine, L_N, N_LAYERS - L_N, PNRF_NET_NERFCLS, "fine"}};
+  const float *W[3][N_LAYERS], *b[3][N_LAYERS];
+  int in_dim[3][N_LAYERS], out_dim[3][N_LAYERS];
+  for (int pass = 0; pass < 2; ++pass)      // every refusal first, for all three, then the launches
+    for (int i = 0; i < 3; ++i) {
+      const Net& n = nets[i];
+      if (!n.h) continue;
+      if (pass == 0) {
+        PNRF_REQUIRE(n.h->net == n.kind, PNRF_E_SHAPE, "pnrf_trainer_publish: the %s handle is of net kind %d, the trainer's %s net is of kind %d", n.name, n.h->net, n.name, n.kind);
+        for (int l = 0; l < n.count; ++l) {
+          const TLin& L = t->L[n.first + l];
+          W[i][l] = t->P + L.w; b[i][l] = t->P + L.b; in_dim[i][l] = L.in; out_dim[i][l] = L.out;
+        }
+      }
+      const int rc = pass == 0 ? repack_prepare(n.h, W[i], b[i], in_dim[i], out_dim[i], n.count) : pnrf_mlp_repack(n.h, W[i], b[i], in_dim[i], out_dim[i], n.count, stream);
+      if (rc) return rc;
+    }
+  return 0;
+}
+
 // captured iterations hold the kernel selection of the moment they were captured: every configuration change drops them
 static void drop_graphs(pnrf_trainer* t) {
   for (auto& g : t->graphs) (void)hipGraphExecDestroy(g.exec);

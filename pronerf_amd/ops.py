@@ -83,6 +83,24 @@ class PackedMLP:
         check(lib.pnrf_mlp_pack_image(net, *args, buf, size.value, C.byref(size)), 'pnrf_mlp_pack_image')
         return bytes(buf)
 
+    def repack(self, weights, biases):
+        """Rewrite the handle's weights in place, on the device, from float32 GPU tensors W[out, in] / b[out] of the handle's shape (pnrf_mlp_repack):
+        kernels on the current stream write the bytes ``pack_image(net, weights, biases)`` holds into the handle's buffers, at the same addresses, so a
+        ``Context``, ``Renderer`` or ``PoseGraph`` built on the handle renders the new weights from its next launch in stream order.  No host
+        synchronisation; from the second call on nothing is allocated, and the call can be captured in a graph.  Another shape or net kind raises
+        ``PnrfError`` and leaves the handle as it was.  -> self.  (``Renderer.calibrate()`` depends on the weights: call it again if it matters.)"""
+        n = len(weights)
+        if len(biases) != n:
+            raise PnrfError(f'repack: {n} weight matrices, {len(biases)} bias vectors')
+        ws = [_chk(w, f'weights[{l}]') for l, w in enumerate(weights)]
+        bs = [_chk(b, f'biases[{l}]') for l, b in enumerate(biases)]
+        if any(w.dim() != 2 for w in ws) or any(b.dim() != 1 or b.shape[0] != w.shape[0] for w, b in zip(ws, bs)):
+            raise PnrfError('repack: expected W[out, in] matrices and b[out] vectors')
+        args = ((C.c_void_p * n)(*[w.data_ptr() for w in ws]), (C.c_void_p * n)(*[b.data_ptr() for b in bs]),
+                (C.c_int * n)(*[w.shape[1] for w in ws]), (C.c_int * n)(*[w.shape[0] for w in ws]), n)
+        check(_lib.load().pnrf_mlp_repack(self.handle, *args, _stream()), 'pnrf_mlp_repack')
+        return self
+
     def set_variant(self, variant):
         """Configuration step (before the handle is used by a context / stream)."""
         if variant not in _lib.VARIANTS:
@@ -1230,6 +1248,20 @@ class Trainer:
             check(_lib.load().pnrf_trainer_write(self.handle, k, layer, _ptr(W), _ptr(b), _stream()), 'pnrf_trainer_write')
 
     _KINDS = {'param': 0, 'grad': 1, 'm': 2, 'v': 3, 'm_nerf': 4, 'v_nerf': 5}
+
+    def publish(self, sampler=None, refine=None, fine=None):
+        """Repack ``PackedMLP`` handles in place from the trainer's own device parameters (pnrf_trainer_publish; kernels on the current stream, no host
+        synchronisation, no read-back): ``sampler`` from trainer layers 0-6, ``refine`` from 7-13, ``fine`` — a NeRF-class handle — from 14-25.  Any of
+        them may be None.  Reads only: allowed between ``forward`` and ``backward``.  A handle of another kind or shape raises ``PnrfError`` before
+        anything is launched.  What is built on the handles (``Renderer``, ``RenderContext``, ``PoseGraph``) renders the published weights from its
+        next launch in stream order; ``Renderer.calibrate()`` may be called again afterwards, its choice depends on the weights."""
+        for name, h in (('sampler', sampler), ('refine', refine), ('fine', fine)):
+            if h is not None and not isinstance(h, PackedMLP):
+                raise PnrfError(f'Trainer.publish: {name} must be a PackedMLP or None')
+        hp = [C.c_void_p(0) if h is None else h.handle for h in (sampler, refine, fine)]
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_trainer_publish(self.handle, *hp, _stream()), 'pnrf_trainer_publish')
+        return self
 
     def flat(self, kind='grad'):
         """Zero-copy torch view [nparam] of one of the trainer's flat device arrays (all layers, trainer order) — e.g. for

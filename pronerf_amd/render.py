@@ -199,6 +199,13 @@ class Renderer:
         with torch.cuda.device(self.device):
             return ops.frame_rays(K, c2w, H, W, first=first, count=count, device=self.device, block=block, stride=stride)
 
+    def publish_from(self, trainer):
+        """Follow a trainer: repack the three handles in place from ``trainer``'s device parameters (``ops.Trainer.publish``), on the current stream.
+        The context, the scene and every ``PoseGraph`` captured from this renderer stay valid and render the new weights from their next launch in
+        stream order.  ``calibrate()`` may be called again afterwards: its choice depends on the weights.  -> self"""
+        trainer.publish(sampler=self.sampler, refine=self.refine, fine=self.nerf)
+        return self
+
     def calibrate(self, rays, or_rays, threshold=0.55):
         """Pick the sampler form for THESE nets from one rendered frame (once per checkpoint, outside any timed loop; waits for the device).
         A sampler that has learned surfaces bunches its 8 depths there and the two-pass form re-renders most rays (68.7 % on the scene-trained

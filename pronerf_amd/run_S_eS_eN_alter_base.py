@@ -236,7 +236,7 @@ def train(argv=None, device='cuda'):
             print('Saved checkpoints at', path)
         if i % args.i_testset == 0 and i > 0 and replica == 0:                                                  # :984-996
             ps = evaluate_views(tr, 1, poses[i_test], images[i_test], images[i_train], poses[i_train], K, H, W,
-                                savedir=os.path.join(out_root, 'testset_{:06d}'.format(i)), near=1e-6, white_bkgd=args.white_bkgd)
+                                savedir=os.path.join(out_root, 'testset_{:06d}'.format(i)), near=1e-6, white_bkgd=args.white_bkgd, path=args.testset_path)
             print(f'[TEST] Iter: {i} PSNR per view: {[round(p, 2) for p in ps]} mean {float(np.mean(ps)):.2f}')
             log.append((i, 'test_psnr', float(np.mean(ps))))
         if i % args.i_print == 0 or i == n_iters - 1:

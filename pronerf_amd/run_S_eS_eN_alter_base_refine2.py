@@ -261,15 +261,52 @@ def shared_permutation(n, epoch, dev):
     return torch.randperm(n, generator=gen).to(dev)
 
 
-def evaluate_views(tr, stage, test_poses, test_images, train_images, train_poses, K, H, W, savedir=None, near=0., white_bkgd=False):
+def eval_renderer(tr, train_images, train_poses, K, H, W):
+    """The ``Renderer`` (with the ``ops.Scene`` of the training views) that ``evaluate_views(path='render')`` keeps with the trainer: packed once
+    from the trainer's state dicts, afterwards only repacked in place (``Renderer.publish_from``).  ``Renderer.calibrate()`` may be called on it
+    again after a publish: its choice depends on the weights."""
+    from .render import Renderer
+    key = (int(H), int(W), len(train_images))
+    cached = getattr(tr, '_eval_renderer', None)
+    if cached is None or cached[0] != key:
+        s_sd, r_sd, f_sd = state_dicts_from_trainer(tr)
+        nets = {'sampler': (s_sd, _MM_KEYS), 'refine': (r_sd, _MM_KEYS), 'nerf': (f_sd, _FINE_KEYS)}
+        weights = {n: {'W': [sd[k + '.weight'] for k in keys], 'b': [sd[k + '.bias'] for k in keys]} for n, (sd, keys) in nets.items()}
+        r = Renderer(weights, H * W, device=tr.device)
+        r.set_scene(np.asarray(train_poses, dtype=np.float32)[:, :3, :4], np.asarray(train_images, dtype=np.float32), np.asarray(K, dtype=np.float32))
+        tr._eval_renderer = cached = (key, r)
+    return cached[1]
+
+
+def evaluate_views(tr, stage, test_poses, test_images, train_images, train_poses, K, H, W, savedir=None, near=0., white_bkgd=False, path='train'):
     """The periodic test-set render of the training scripts (refine2.py:905-917, base.py:984-996): every hold-out view through
     the evaluation branch of the stage's own ``render_rays`` (nearest ``num_neighbor`` training views of the target pose, no
     jitter / exploration / noise) with the trainer's current weights, on the training-time forward kernels.  stage 2: eps 1e-5,
     neighbour-major epi; stage 1: eps 1e-6, sample-major epi, raw clamp 10.  Returns the PSNR of each view; writes
-    ``{i:03d}.png`` into ``savedir`` if given."""
+    ``{i:03d}.png`` into ``savedir`` if given.
+
+    path='render' (``--testset_path render``): the views as a user will see them — the trainer's weights are published on the device into a
+    ``Renderer`` kept with the trainer (``eval_renderer``; no read-back, no new handles) and every pose goes through ``Renderer.render_pose``, the
+    fused inference kernels at their default precisions (neighbour-major epi, no raw clamp, black background); PSNR from ``ops.image_metrics``."""
     import os
     from .run_S_eS_eN_alter_trt import _write_png
     dev = tr.device
+    if path == 'render':
+        r = eval_renderer(tr, train_images, train_poses, K, H, W)
+        eps = 1e-5 if stage == 2 else 1e-6
+        psnrs = []
+        with torch.cuda.device(dev):
+            r.publish_from(tr)
+            for i, (c2w, gt) in enumerate(zip(np.asarray(test_poses, dtype=np.float32), np.asarray(test_images, dtype=np.float32))):
+                rgb = r.render_pose(c2w[:3, :4], H, W, near=near, far=1., eps=eps)[:, :3].reshape(H, W, 3)
+                mse = float(ops.image_metrics(rgb, torch.as_tensor(gt, device=dev))[1])
+                psnrs.append(-10.0 * np.log10(max(mse, 1e-12)))
+                if savedir is not None:
+                    os.makedirs(savedir, exist_ok=True)
+                    _write_png(os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgb.cpu().numpy()))
+        return psnrs
+    if path != 'train':
+        raise ops.PnrfError(f"evaluate_views: path must be 'train' or 'render', got {path!r}")
     s_sd, r_sd, f_sd = state_dicts_from_trainer(tr)
     sampler = ops.PackedMLP(ops.NET_SAMPLER, [s_sd[k + '.weight'] for k in _MM_KEYS], [s_sd[k + '.bias'] for k in _MM_KEYS])
     refine = ops.PackedMLP(ops.NET_REFINE, [r_sd[k + '.weight'] for k in _MM_KEYS], [r_sd[k + '.bias'] for k in _MM_KEYS])
@@ -478,7 +515,7 @@ def train(argv=None, device='cuda', loss_fn=None, patch_size=0):
             print('Saved checkpoints at', path)
         if i % args.i_testset == 0 and i > 0 and replica == 0:                                                  # :905-917
             ps = evaluate_views(tr, 2, poses[i_test], images[i_test], images[i_train], poses[i_train], K, H, W,
-                                savedir=os.path.join(out_root, 'testset_{:06d}'.format(i)), white_bkgd=args.white_bkgd)
+                                savedir=os.path.join(out_root, 'testset_{:06d}'.format(i)), white_bkgd=args.white_bkgd, path=args.testset_path)
             print(f'[TEST] Iter: {i} PSNR per view: {[round(p, 2) for p in ps]} mean {float(np.mean(ps)):.2f}')
             log.append((i, 'test_psnr', float(np.mean(ps))))
         if i % args.i_print == 0 or i == n_iters - 1:
