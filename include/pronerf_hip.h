@@ -627,6 +627,30 @@ int pnrf_ssim_loss_fwd(const float* pred, int pred_stride, int64_t pred_patch_st
 #define PNRF_TO8B_WORKSPACE_BYTES 4096
 int pnrf_frame_to8b_fwd(const float* rgb, int rgb_stride, const float* depth, int depth_stride, int64_t n,
                         uint8_t* rgb8, uint8_t* depth8, void* workspace, int64_t workspace_bytes, void* stream);
+/* An 8-bit plane as the bytes of a PNG file (csrc/pnrf_png_rules.h states the format rules once, for the host twin and the kernels).
+ * img: H rows of W pixels of `channels` bytes (1: gray, 3: RGB), row y at img + y row_stride, row_stride in bytes >= W channels: the planes of
+ * pnrf_frame_to8b_fwd as they stand.  filter: -1 adaptive (per row the type with the smallest sum of |residual as a signed byte|, ties to the lowest
+ * type), 0 .. 4 that type on every row.  The file: signature, IHDR (8 bit, colour type 0 or 2, no interlace), one IDAT, IEND.  The IDAT's zlib stream
+ * is coded in independent segments of pnrf_png_segment_rows() rows of filtered bytes: literals and distance-1 matches of 3 .. 258 bytes, one dynamic
+ * Huffman block (code lengths from the segment's histogram, at most 15 bits) or stored blocks where those are smaller, and behind every segment but
+ * the last an empty stored block (00 00 FF FF after padding).  Adler-32 and CRC-32 are taken per piece and combined.  Deterministic: the same pixels
+ * give the same bytes from pnrf_png_encode_host, from pnrf_png_encode_fwd, on any stream.
+ * pnrf_png_max_bytes: an upper bound of the file for any content (raw + 5 raw / 65535 + 10 segments + 63 with raw = H (W channels + 1));
+ * pnrf_png_workspace_bytes: the device workspace of pnrf_png_encode_fwd; both 0 for sizes the calls refuse.
+ * pnrf_png_encode_host: HOST pointers, plain C++: the twin the device bytes are held to.  size: HOST, receives the file's length.
+ * pnrf_png_encode_fwd: dev pointers, four launches in stream order, nothing allocated or read back, capturable in a graph.  out receives the
+ * file, size_dev (dev int64, 8-byte aligned) its length.  workspace: dev, 16-byte aligned, >= pnrf_png_workspace_bytes, contents irrelevant;
+ * concurrent calls need separate workspaces.
+ * PNRF_E_ARG before any launch: H or W < 1, H W > 2^28, channels not 1 or 3, filter outside -1 .. 4, row_stride < W channels,
+ * capacity < pnrf_png_max_bytes, a workspace that is too small or misaligned, a null pointer. */
+int pnrf_png_segment_rows(void);
+int64_t pnrf_png_max_bytes(int H, int W, int channels);
+int64_t pnrf_png_workspace_bytes(int H, int W, int channels);
+int pnrf_png_encode_host(const uint8_t* img_host, int64_t row_stride, int H, int W, int channels, int filter,
+                         uint8_t* out_host, int64_t capacity, int64_t* size);
+int pnrf_png_encode_fwd(const uint8_t* img, int64_t row_stride, int H, int W, int channels, int filter,
+                        uint8_t* out, int64_t capacity, int64_t* size_dev, void* workspace, int64_t workspace_bytes,
+                        void* stream);
 
 /* ---- LPIPS (version 0.1) of an image pair: AlexNet / VGG-16 feature stacks and the metric ---------------------
  * The third number the method is reported with (run_nerf_helpers.py:137-149: rgb_lpips, nets 'alex' and 'vgg').  The weights are the caller's:

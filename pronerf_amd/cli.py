@@ -65,6 +65,8 @@ def infer_argv(ns):
             argv += ['--' + k, getattr(ns, k)]
     if getattr(ns, 'device_to8b', False):
         argv.append('--device_to8b')
+    if getattr(ns, 'device_png', False):
+        argv.append('--device_png')
     if getattr(ns, 'scene_cache', None) is not None:
         argv += ['--scene_cache', ns.scene_cache]
     return argv + _extra(ns)
@@ -122,6 +124,7 @@ def build_parser():
         q.add_argument('--lpips_backbone', '--lpips-backbone', default=None, dest='lpips_backbone', help="the torchvision state dict of the backbone (a file the user brings)")
         q.add_argument('--lpips_lin', '--lpips-lin', default=None, dest='lpips_lin', help="the lpips package's weights/v0.1/<net>.pth (a file the user brings)")
         q.add_argument('--device_to8b', '--device-to8b', action='store_true', dest='device_to8b', help='8-bit PNG planes converted on the device')
+        q.add_argument('--device_png', '--device-png', action='store_true', dest='device_png', help='PNG files encoded on the device (smaller files, no host compression)')
         q.add_argument('--scene_cache', '--scene-cache', choices=['f32', 'u8'], default=None, dest='scene_cache',
                        help="source views resident on the device, every pose rendered from its twelve floats ('u8': RGBA8 texels)")
 

@@ -47,6 +47,9 @@ _VARIANT = {
             # not in the reference: 'psnr,ssim' takes PSNR and SSIM of the hold-out views on the device (render_path's pnrf_metrics); device_to8b hands
             # the PNG writer 8-bit planes converted on the device (pnrf_device_to8b)
             ('metrics', str, 'psnr'), ('device_to8b', 'flag', False),
+            # not in the reference: device_png encodes a pose's two PNG files on the device (render_path's pnrf_device_png, ops.PngEncoder): the planes
+            # of ops.frame_to8b never travel, the writer thread only writes the finished bytes
+            ('device_png', 'flag', False),
             # not in the reference: 'psnr,ssim,lpips' also takes LPIPS (render_path's pnrf_lpips, an ops.Lpips) with the net lpips_net ('alex' | 'vgg': the
             # one NeRF-family tables report) from the two weight files the user brings: the torchvision state dict of the backbone and the lpips package's lin file
             ('lpips_net', str, 'vgg'), ('lpips_backbone', str, None), ('lpips_lin', str, None),

@@ -1113,6 +1113,102 @@ def frame_to8b(rgb=None, depth=None, rgbd=None):
     return rgb8, depth8
 
 
+# ------------------------------------------------------------------------------------------ PNG files of an 8-bit plane
+PNG_FILTERS = {'adaptive': -1, 'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4}
+
+
+def _png_filter(filter):
+    f = PNG_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not -1 <= int(f) <= 4:
+        raise PnrfError(f'png: filter {filter!r}; one of {sorted(PNG_FILTERS)} or -1 .. 4')
+    return int(f)
+
+
+def png_segment_rows():
+    """Rows of filtered bytes per independently coded segment of the encoder's zlib stream (a constant of csrc/pnrf_png_rules.h)."""
+    return int(_lib.load().pnrf_png_segment_rows())
+
+
+def png_max_bytes(H, W, channels):
+    """Upper bound of the PNG file of an H x W plane of ``channels`` (1 or 3) bytes per pixel, for any content (pnrf_png_max_bytes)."""
+    return int(_lib.load().pnrf_png_max_bytes(int(H), int(W), int(channels)))
+
+
+def png_encode_host(img, filter='adaptive'):
+    """The PNG file (``bytes``) of a uint8 numpy image [H,W] or [H,W,3] from the host twin of the device encoder (pnrf_png_encode_host):
+    the same bytes as ``PngEncoder.encode``.  Rows may be strided (a view with a larger row pitch is read as it stands)."""
+    lib = _lib.load()
+    if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)):
+        raise PnrfError(f'png_encode_host: expected a uint8 numpy array [H,W] or [H,W,3], got {getattr(img, "dtype", type(img))} {getattr(img, "shape", ())}')
+    H, W = int(img.shape[0]), int(img.shape[1])
+    ch = 1 if img.ndim == 2 else int(img.shape[2])
+    dense = img.strides[-1] == 1 and (img.ndim == 2 or img.strides[1] == ch)      # a row's bytes lie together
+    if not (dense and img.strides[0] >= W * ch) or H * W == 0:
+        img = np.ascontiguousarray(img)
+    stride = int(img.strides[0]) if H * W else W * ch
+    cap = max(png_max_bytes(H, W, ch), 64)
+    out = np.empty(cap, np.uint8)
+    size = C.c_int64(0)
+    check(lib.pnrf_png_encode_host(C.c_void_p(img.ctypes.data), stride, H, W, ch, _png_filter(filter), C.c_void_p(out.ctypes.data), cap, C.byref(size)),
+          'pnrf_png_encode_host')
+    return out[:size.value].tobytes()
+
+
+class PngEncoder:
+    """PNG files of H x W uint8 planes (channels 1: gray, 3: RGB) encoded on the device (pnrf_png_encode_fwd).  Owns the workspace, the output
+    buffer of ``png_max_bytes``, a pinned host buffer of the same size and the device cell that receives the file's length; ``encode`` allocates
+    nothing and works in stream order, so it can be captured in a graph."""
+
+    def __init__(self, H, W, channels, device):
+        lib = _lib.load()
+        self.H, self.W, self.channels = int(H), int(W), int(channels)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise PnrfError('PngEncoder: expected a GPU device (pronerf_amd has no CPU path; png_encode_host is the host twin)')
+        self.max_bytes = int(lib.pnrf_png_max_bytes(self.H, self.W, self.channels))
+        self.workspace_bytes = int(lib.pnrf_png_workspace_bytes(self.H, self.W, self.channels))
+        if self.max_bytes <= 0:
+            raise PnrfError(f'PngEncoder: {self.H} x {self.W} x {self.channels} is outside what the encoder takes (sides >= 1, H W <= 2^28, 1 or 3 channels)')
+        self.out = torch.empty(self.max_bytes, device=self.device, dtype=torch.uint8)
+        self.workspace = torch.empty(self.workspace_bytes, device=self.device, dtype=torch.uint8)
+        self.size = torch.zeros(1, device=self.device, dtype=torch.int64)
+        self.host = torch.empty(self.max_bytes, dtype=torch.uint8).pin_memory()
+        self.host_size = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+    def _plane(self, img):
+        if not isinstance(img, torch.Tensor) or not img.is_cuda:
+            raise PnrfError('PngEncoder: expected a GPU tensor (pronerf_amd has no CPU path)')
+        want = (self.H, self.W) if self.channels == 1 else (self.H, self.W, 3)
+        if img.dtype != torch.uint8 or tuple(img.shape) != want or img.device != self.device:
+            raise PnrfError(f'PngEncoder: expected a uint8 tensor {list(want)} on {self.device}, got {img.dtype} {tuple(img.shape)} on {img.device}')
+        st = img.stride()
+        if not (st[-1] == 1 and (self.channels == 1 or st[1] == 3) and st[0] >= self.W * self.channels):
+            img = img.contiguous()
+        return img, int(img.stride(0))
+
+    def launch(self, img, filter='adaptive'):
+        """The encoder's launches on the current stream; the file is then in ``self.out``, its length in ``self.size``.  Returns nothing: no sync."""
+        img, stride = self._plane(img)
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_png_encode_fwd(_ptr(img), stride, self.H, self.W, self.channels, _png_filter(filter), _ptr(self.out), self.max_bytes, _ptr(self.size),
+                                                  _ptr(self.workspace), self.workspace_bytes, _stream()), 'pnrf_png_encode_fwd')
+
+    def encode(self, img, filter='adaptive'):
+        """-> uint8 device tensor: a view of the finished file in the encoder's output buffer (valid until the next call).  Reads the length
+        back, which synchronises the stream; ``launch`` does not."""
+        self.launch(img, filter)
+        return self.out[:int(self.size.item())]
+
+    def encode_to_host(self, img, filter='adaptive'):
+        """-> ``bytes`` of the file: the launches, one asynchronous copy of ``max_bytes`` and of the length into pinned memory, one sync, a slice."""
+        self.launch(img, filter)
+        with torch.cuda.device(self.device):
+            self.host.copy_(self.out, non_blocking=True)
+            self.host_size.copy_(self.size, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        return self.host[:int(self.host_size[0])].numpy().tobytes()
+
+
 # ------------------------------------------------------------------------------------------ stage-2 training step
 def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0.0, white_bkgd=False):
     """raw2outputs backward for d rgb_map -> (d_raw, d_z, d_add, d_mul); d_add / d_mul are None without add / mul.  rays_d may be a

@@ -367,6 +367,11 @@ def _write_png(path, img_u8):
                 chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
 
 
+def _write_bytes(path, data):
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0, near=0., far=1.,
                 or_near=1., or_far=10., n_timing_reps=20, verbose=True):
     """Render every pose (run_S_eS_eN_alter_trt.py:223-375): per-frame set-up, ``n_timing_reps``
@@ -379,6 +384,8 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     ``pnrf_metrics`` takes PSNR and SSIM (helpers:151-197) of every pose against ``gt_imgs[i]`` from one ``ops.image_metrics`` call on the
     rendered rows, read back together, into ``render_kwargs['psnrs']`` / ``['ssims']``; ``pnrf_device_to8b`` encodes a pose's two PNGs
     from ``ops.frame_to8b``'s uint8 planes (same bytes as ``to8b`` on the host).  The returned float arrays are the same either way.
+    ``pnrf_device_png`` goes one step further: those planes stay on the device and both PNG files are encoded there (``ops.PngEncoder``; rank 0
+    encodes the gathered frame under ``torchrun``), the worker thread writes the finished bytes; the files decode to the same pixels and are smaller.
     ``pnrf_lpips`` (an ``ops.Lpips``) takes LPIPS of every pose against ``gt_imgs[i]`` on the rendered rows, into ``render_kwargs['lpips']``.
 
     ``pnrf_scene_cache`` = 'f32' | 'u8' (opt-in as well) keeps the source views on the device (``ops.Scene``, built once from ``images`` / ``poses`` /
@@ -399,6 +406,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     rgbs0, rgbs1, depths, psnrs, times, walls = [], [], [], [], [], []
     dev_metrics, dev_to8b, ssims = bool(render_kwargs.get('pnrf_metrics')), bool(render_kwargs.get('pnrf_device_to8b')), []
     lpips_fn, lpips_vals = render_kwargs.get('pnrf_lpips'), []
+    dev_png, png_enc = bool(render_kwargs.get('pnrf_device_png')), None
     from concurrent.futures import ThreadPoolExecutor
     from .dist import FrameGather, world as _world
     from .render import RayPartition
@@ -499,7 +507,13 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
                     lpips_vals.append(float(lpips_fn(torch.as_tensor(gt_imgs[i], dtype=torch.float32).to(dev), rgb1)))
             if png_pool is not None:
                 os.makedirs(savedir, exist_ok=True)
-                if dev_to8b:         # the two 8-bit planes come from the device into pinned memory: 4 bytes per pixel instead of 16, no to8b / np.max on the host
+                if dev_png:          # both files leave the device as their finished bytes (ops.PngEncoder); the worker thread only writes them
+                    if png_enc is None:
+                        png_enc = (ops.PngEncoder(H, W, 3, dev), ops.PngEncoder(H, W, 1, dev))
+                    rgb8, depth8 = ops.frame_to8b(rgb1, depth_map)
+                    png_jobs.append(png_pool.submit(_write_bytes, os.path.join(savedir, '{:03d}.png'.format(i)), png_enc[0].encode_to_host(rgb8)))
+                    png_jobs.append(png_pool.submit(_write_bytes, os.path.join(savedir, 'depth_{:03d}.png'.format(i)), png_enc[1].encode_to_host(depth8)))
+                elif dev_to8b:       # the two 8-bit planes come from the device into pinned memory: 4 bytes per pixel instead of 16, no to8b / np.max on the host
                     planes = [torch.empty(t.shape, dtype=torch.uint8).pin_memory().copy_(t, non_blocking=True) for t in ops.frame_to8b(rgb1, depth_map)]
                     torch.cuda.current_stream(dev).synchronize()
                     png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, '{:03d}.png'.format(i)), planes[0].numpy()))
@@ -617,6 +631,7 @@ def train(argv=None, device='cuda'):
     if 'lpips' in metrics:
         kw['pnrf_lpips'] = lpips_from_args(args, device)        # raises before anything is rendered when a weight file is missing
     kw['pnrf_device_to8b'] = bool(getattr(args, 'device_to8b', False))
+    kw['pnrf_device_png'] = bool(getattr(args, 'device_png', False))
     if getattr(args, 'scene_cache', None) not in (None, 'None', 'off'):
         kw['pnrf_scene_cache'] = args.scene_cache
     if args.max_images is not None:
