@@ -164,8 +164,7 @@ def test_placement_sampler_split_and_pass1(dev, D, skips):
     """The two kernels on log2(e)-scaled streams (module docstring, 2.): pass 1 (the two-pass default: every ray of these nets is decided, so its rows are
     pass 1's; asserted) and the split-fp16 kernel, NARROW and WIDE.  add / mul within mmskips_ref.SCALED_TOL = 1e-3 of the exact integers (derived there:
     lo-plane residuals of the pre-image weights, < 4e-4), the sort order the one the head's biases fix.
-    One gap: the integer inputs have a lo plane of exactly 0, so pass 1's W_hi P_lo product and the lo-plane B operand of the split kernel's ninth k-step are
-    multiplied by zero — a wrong P_lo operand is invisible here and is held by the stage and index-evidence tests (real rays) alone."""
+    The integer inputs and activations here have lo planes of 0: the products with P_lo and X_lo' are held by tests/test_exact_sampler_gpu.py (x_big, hid_big)."""
     from pronerf_amd import ops
     net = ms.sampler_scaled_net(D, list(skips))
     W, b = ms.sampler_pack_weights(net)
