@@ -651,6 +651,30 @@ int pnrf_png_encode_host(const uint8_t* img_host, int64_t row_stride, int H, int
 int pnrf_png_encode_fwd(const uint8_t* img, int64_t row_stride, int H, int W, int channels, int filter,
                         uint8_t* out, int64_t capacity, int64_t* size_dev, void* workspace, int64_t workspace_bytes,
                         void* stream);
+/* An 8-bit plane as the bytes of a baseline JPEG file (csrc/pnrf_jpeg_rules.h states the format rules once, for the host twin and the kernels).
+ * img as for pnrf_png_encode_fwd: 1 channel is coded as one gray component, 3 as Y, Cb, Cr (JFIF full-range BT.601 in 16-bit fixed point) without
+ * subsampling, one block of each per MCU.  quality 1 .. 100: the Annex K tables in the IJG library's scaling, entries 1 .. 255.  The file: SOI, APP0
+ * (JFIF 1.01), DQT, SOF0, DHT (the Annex K.3 tables as they stand), DRI, SOS, entropy data, EOI.  Right and bottom edges are padded to a multiple of 8
+ * by replication; the forward DCT is the 13-bit scaled integer form with 32-bit intermediates; quantisation divides rounding half away from zero.
+ * Every MCU row is one restart interval (DRI = ceil(W / 8)), coded on its own: DC predictions start at 0, the last byte is filled with 1-bits, RSTm
+ * (m = row mod 8) follows every interval but the last; every FF byte of entropy data is followed by 00.  Deterministic: the same pixels give the same
+ * bytes from pnrf_jpeg_encode_host, from pnrf_jpeg_encode_fwd, on any stream.
+ * pnrf_jpeg_max_bytes: an upper bound of the file for any content: header (330 gray, 613 colour) + ceil(H / 8) (2 ceil(1660 blocks / 8) + 2) + 2 with
+ * blocks = ceil(W / 8) channels a row, 1660 = 22 DC bits + 63 x 26 AC bits, doubled for stuffing, 2 for RSTm;
+ * pnrf_jpeg_workspace_bytes: the device workspace of pnrf_jpeg_encode_fwd; both 0 for sizes the calls refuse.
+ * pnrf_jpeg_encode_host: HOST pointers, plain C++: the twin the device bytes are held to.  size: HOST, receives the file's length.
+ * pnrf_jpeg_encode_fwd: dev pointers, four launches in stream order, nothing allocated or read back, capturable in a graph.  out receives the
+ * file, size_dev (dev int64, 8-byte aligned) its length.  workspace: dev, 16-byte aligned, >= pnrf_jpeg_workspace_bytes, contents irrelevant;
+ * concurrent calls need separate workspaces.
+ * PNRF_E_ARG before any launch: H or W outside 1 .. 65535, channels not 1 or 3, quality outside 1 .. 100, row_stride < W channels,
+ * capacity < pnrf_jpeg_max_bytes, a workspace that is too small or misaligned, a null pointer. */
+int64_t pnrf_jpeg_max_bytes(int H, int W, int channels);
+int64_t pnrf_jpeg_workspace_bytes(int H, int W, int channels);
+int pnrf_jpeg_encode_host(const uint8_t* img_host, int64_t row_stride, int H, int W, int channels, int quality,
+                          uint8_t* out_host, int64_t capacity, int64_t* size);
+int pnrf_jpeg_encode_fwd(const uint8_t* img, int64_t row_stride, int H, int W, int channels, int quality,
+                         uint8_t* out, int64_t capacity, int64_t* size_dev, void* workspace, int64_t workspace_bytes,
+                         void* stream);
 
 /* ---- LPIPS (version 0.1) of an image pair: AlexNet / VGG-16 feature stacks and the metric ---------------------
  * The third number the method is reported with (run_nerf_helpers.py:137-149: rgb_lpips, nets 'alex' and 'vgg').  The weights are the caller's:

@@ -86,6 +86,11 @@ SIGNATURES = {
     'pnrf_png_workspace_bytes': (_i64, [_i, _i, _i]),
     'pnrf_png_encode_host': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i64, C.POINTER(_i64)]),
     'pnrf_png_encode_fwd': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i64, _p, _p, _i64, _p]),
+    # JPEG files of an 8-bit plane: host twin and device encoder
+    'pnrf_jpeg_max_bytes': (_i64, [_i, _i, _i]),
+    'pnrf_jpeg_workspace_bytes': (_i64, [_i, _i, _i]),
+    'pnrf_jpeg_encode_host': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i64, C.POINTER(_i64)]),
+    'pnrf_jpeg_encode_fwd': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i64, _p, _p, _i64, _p]),
     # LPIPS: feature stacks and the metric
     'pnrf_lpips_create': (_i, [C.c_char_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), _i, C.POINTER(_p), C.POINTER(_i), C.POINTER(_p)]),
     'pnrf_lpips_free': (_i, [_p]),

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libpronerf_hip.so')
-SOURCES = ['pnrf_pack.hip', 'pnrf_repack.hip', 'pnrf_ops.hip', 'pnrf_mlp_kernels.hip', 'pnrf_train.hip', 'pnrf_image.hip', 'pnrf_png.hip', 'pnrf_lpips.hip', 'pnrf_scene.hip', 'pnrf_batch.hip']
+SOURCES = ['pnrf_pack.hip', 'pnrf_repack.hip', 'pnrf_ops.hip', 'pnrf_mlp_kernels.hip', 'pnrf_train.hip', 'pnrf_image.hip', 'pnrf_png.hip', 'pnrf_jpeg.hip', 'pnrf_lpips.hip', 'pnrf_scene.hip', 'pnrf_batch.hip']
 LINK = []                    # no library dependencies: every kernel, the training step's layer products included, is in csrc/
 ARCH = 'gfx950'
 # No packed-fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 / v_pk_mov_b32) in any kernel of the library.  Round 5 traced round 4's "co-residency

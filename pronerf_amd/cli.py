@@ -67,6 +67,8 @@ def infer_argv(ns):
         argv.append('--device_to8b')
     if getattr(ns, 'device_png', False):
         argv.append('--device_png')
+    if getattr(ns, 'video', False):
+        argv += ['--video', '--video_fps', str(ns.video_fps), '--video_quality', str(ns.video_quality)]
     if getattr(ns, 'scene_cache', None) is not None:
         argv += ['--scene_cache', ns.scene_cache]
     return argv + _extra(ns)
@@ -125,6 +127,9 @@ def build_parser():
         q.add_argument('--lpips_lin', '--lpips-lin', default=None, dest='lpips_lin', help="the lpips package's weights/v0.1/<net>.pth (a file the user brings)")
         q.add_argument('--device_to8b', '--device-to8b', action='store_true', dest='device_to8b', help='8-bit PNG planes converted on the device')
         q.add_argument('--device_png', '--device-png', action='store_true', dest='device_png', help='PNG files encoded on the device (smaller files, no host compression)')
+        q.add_argument('--video', action='store_true', dest='video', help='also write the rendered poses as Motion-JPEG: video.avi and video_depth.avi, frames encoded on the device')
+        q.add_argument('--video_fps', '--video-fps', type=float, default=30.0, dest='video_fps', help='frames per second of --video')
+        q.add_argument('--video_quality', '--video-quality', type=int, default=90, dest='video_quality', help='JPEG quality 1 .. 100 of --video')
         q.add_argument('--scene_cache', '--scene-cache', choices=['f32', 'u8'], default=None, dest='scene_cache',
                        help="source views resident on the device, every pose rendered from its twelve floats ('u8': RGBA8 texels)")
 

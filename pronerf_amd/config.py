@@ -50,6 +50,9 @@ _VARIANT = {
             # not in the reference: device_png encodes a pose's two PNG files on the device (render_path's pnrf_device_png, ops.PngEncoder): the planes
             # of ops.frame_to8b never travel, the writer thread only writes the finished bytes
             ('device_png', 'flag', False),
+            # not in the reference: video also writes the rendered poses as Motion-JPEG files video.avi / video_depth.avi (render_path's pnrf_video:
+            # ops.JpegEncoder frames of quality video_quality, video.MjpegAviWriter at video_fps frames per second)
+            ('video', 'flag', False), ('video_fps', float, 30.0), ('video_quality', int, 90),
             # not in the reference: 'psnr,ssim,lpips' also takes LPIPS (render_path's pnrf_lpips, an ops.Lpips) with the net lpips_net ('alex' | 'vgg': the
             # one NeRF-family tables report) from the two weight files the user brings: the torchvision state dict of the backbone and the lpips package's lin file
             ('lpips_net', str, 'vgg'), ('lpips_backbone', str, None), ('lpips_lin', str, None),

@@ -1209,6 +1209,94 @@ class PngEncoder:
         return self.host[:int(self.host_size[0])].numpy().tobytes()
 
 
+# ------------------------------------------------------------------------------------------ JPEG files of an 8-bit plane
+def jpeg_max_bytes(H, W, channels):
+    """Upper bound of the JPEG file of an H x W plane of ``channels`` (1 or 3) bytes per pixel, for any content and quality (pnrf_jpeg_max_bytes)."""
+    return int(_lib.load().pnrf_jpeg_max_bytes(int(H), int(W), int(channels)))
+
+
+def _jpeg_quality(quality):
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise PnrfError(f'jpeg: quality {quality!r}; an integer 1 .. 100')
+    return int(quality)
+
+
+def jpeg_encode_host(img, quality=90):
+    """The baseline JPEG file (``bytes``) of a uint8 numpy image [H,W] (gray) or [H,W,3] (RGB, coded as YCbCr 4:4:4) from the host twin of the
+    device encoder (pnrf_jpeg_encode_host): the same bytes as ``JpegEncoder.encode``.  Rows may be strided."""
+    lib = _lib.load()
+    if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)):
+        raise PnrfError(f'jpeg_encode_host: expected a uint8 numpy array [H,W] or [H,W,3], got {getattr(img, "dtype", type(img))} {getattr(img, "shape", ())}')
+    H, W = int(img.shape[0]), int(img.shape[1])
+    ch = 1 if img.ndim == 2 else int(img.shape[2])
+    dense = img.strides[-1] == 1 and (img.ndim == 2 or img.strides[1] == ch)      # a row's bytes lie together
+    if not (dense and img.strides[0] >= W * ch) or H * W == 0:
+        img = np.ascontiguousarray(img)
+    stride = int(img.strides[0]) if H * W else W * ch
+    cap = max(jpeg_max_bytes(H, W, ch), 64)
+    out = np.empty(cap, np.uint8)
+    size = C.c_int64(0)
+    check(lib.pnrf_jpeg_encode_host(C.c_void_p(img.ctypes.data), stride, H, W, ch, _jpeg_quality(quality), C.c_void_p(out.ctypes.data), cap, C.byref(size)),
+          'pnrf_jpeg_encode_host')
+    return out[:size.value].tobytes()
+
+
+class JpegEncoder:
+    """Baseline JPEG files of H x W uint8 planes (channels 1: gray, 3: RGB as YCbCr 4:4:4) encoded on the device (pnrf_jpeg_encode_fwd).  Owns the
+    workspace, the output buffer of ``jpeg_max_bytes``, a pinned host buffer of the same size and the device cell that receives the file's length;
+    ``launch`` allocates nothing and works in stream order, so it can be captured in a graph."""
+
+    def __init__(self, H, W, channels, device, quality=90):
+        lib = _lib.load()
+        self.H, self.W, self.channels, self.quality = int(H), int(W), int(channels), _jpeg_quality(quality)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise PnrfError('JpegEncoder: expected a GPU device (pronerf_amd has no CPU path; jpeg_encode_host is the host twin)')
+        self.max_bytes = int(lib.pnrf_jpeg_max_bytes(self.H, self.W, self.channels))
+        self.workspace_bytes = int(lib.pnrf_jpeg_workspace_bytes(self.H, self.W, self.channels))
+        if self.max_bytes <= 0:
+            raise PnrfError(f'JpegEncoder: {self.H} x {self.W} x {self.channels} is outside what the encoder takes (sides 1 .. 65535, 1 or 3 channels)')
+        self.out = torch.empty(self.max_bytes, device=self.device, dtype=torch.uint8)
+        self.workspace = torch.empty(self.workspace_bytes, device=self.device, dtype=torch.uint8)
+        self.size = torch.zeros(1, device=self.device, dtype=torch.int64)
+        self.host = torch.empty(self.max_bytes, dtype=torch.uint8).pin_memory()
+        self.host_size = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+    def _plane(self, img):
+        if not isinstance(img, torch.Tensor) or not img.is_cuda:
+            raise PnrfError('JpegEncoder: expected a GPU tensor (pronerf_amd has no CPU path)')
+        want = (self.H, self.W) if self.channels == 1 else (self.H, self.W, 3)
+        if img.dtype != torch.uint8 or tuple(img.shape) != want or img.device != self.device:
+            raise PnrfError(f'JpegEncoder: expected a uint8 tensor {list(want)} on {self.device}, got {img.dtype} {tuple(img.shape)} on {img.device}')
+        st = img.stride()
+        if not (st[-1] == 1 and (self.channels == 1 or st[1] == 3) and st[0] >= self.W * self.channels):
+            img = img.contiguous()
+        return img, int(img.stride(0))
+
+    def launch(self, img, quality=None):
+        """The encoder's launches on the current stream; the file is then in ``self.out``, its length in ``self.size``.  Returns nothing: no sync."""
+        img, stride = self._plane(img)
+        q = self.quality if quality is None else _jpeg_quality(quality)
+        with torch.cuda.device(self.device):
+            check(_lib.load().pnrf_jpeg_encode_fwd(_ptr(img), stride, self.H, self.W, self.channels, q, _ptr(self.out), self.max_bytes, _ptr(self.size),
+                                                   _ptr(self.workspace), self.workspace_bytes, _stream()), 'pnrf_jpeg_encode_fwd')
+
+    def encode(self, img, quality=None):
+        """-> uint8 device tensor: a view of the finished file in the encoder's output buffer (valid until the next call).  Reads the length
+        back, which synchronises the stream; ``launch`` does not."""
+        self.launch(img, quality)
+        return self.out[:int(self.size.item())]
+
+    def encode_to_host(self, img, quality=None):
+        """-> ``bytes`` of the file: the launches, one asynchronous copy of ``max_bytes`` and of the length into pinned memory, one sync, a slice."""
+        self.launch(img, quality)
+        with torch.cuda.device(self.device):
+            self.host.copy_(self.out, non_blocking=True)
+            self.host_size.copy_(self.size, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        return self.host[:int(self.host_size[0])].numpy().tobytes()
+
+
 # ------------------------------------------------------------------------------------------ stage-2 training step
 def composite_bwd(raw, z, rays_d, d_rgb, add=None, mul=None, noise=None, clamp=0.0, white_bkgd=False):
     """raw2outputs backward for d rgb_map -> (d_raw, d_z, d_add, d_mul); d_add / d_mul are None without add / mul.  rays_d may be a

@@ -267,6 +267,53 @@ class Renderer:
                                            count=n, block=block, stride=stride, eps=eps, ws=self._pose_workspace(n), out=out)
         return rgbd
 
+    def render_video(self, poses, H, W, path, fps=30, quality=90, depth_path=None, **pose_args):
+        """The camera path ``poses`` (each [3,4] or [4,4]) as a Motion-JPEG file, with no float read-back: per pose ``render_pose`` from the device-resident
+        scene, ``ops.frame_to8b``, ``ops.JpegEncoder.launch``, then an asynchronous copy of the encoder's ``max_bytes`` and the length into one of two pinned
+        buffers and an event; a writer thread waits for the event and appends the frame (``video.MjpegAviWriter``) while the next pose renders.
+        depth_path: a second, gray file of the depth plane normalised per frame.  pose_args: near / far / or_near / or_far / eps of ``render_pose``.
+        Returns the frames' sizes in bytes, one per pose (pairs (rgb, depth) with depth_path)."""
+        from concurrent.futures import ThreadPoolExecutor
+        from .video import MjpegAviWriter
+        if self.scene is None:
+            raise ops.PnrfError('Renderer.render_video: call set_scene() first')
+        if set(pose_args) - {'near', 'far', 'or_near', 'or_far', 'eps'}:
+            raise ops.PnrfError(f'Renderer.render_video: whole frames only, got {sorted(pose_args)}')
+        planes = 1 if depth_path is None else 2
+        with torch.cuda.device(self.device):
+            encs = [ops.JpegEncoder(H, W, 3 if p == 0 else 1, self.device, quality) for p in range(planes)]
+            pinned = [[(torch.empty(e.max_bytes, dtype=torch.uint8).pin_memory(), torch.zeros(1, dtype=torch.int64).pin_memory()) for e in encs] for _ in range(2)]
+            frame = torch.empty(H * W, 4, device=self.device, dtype=torch.float32)
+            writers = [MjpegAviWriter(path, W, H, fps)] + ([MjpegAviWriter(depth_path, W, H, fps, gray=True)] if planes == 2 else [])
+            pool = ThreadPoolExecutor(max_workers=1)
+
+            def append(event, bufs):
+                event.synchronize()
+                sizes = [int(n[0]) for _, n in bufs]
+                for w, (b, _), n in zip(writers, bufs, sizes):
+                    w.add(b[:n].numpy().tobytes())
+                return sizes[0] if planes == 1 else tuple(sizes)
+
+            jobs = []
+            try:
+                for i, c2w in enumerate(poses):
+                    if i >= 2:
+                        jobs[i - 2].result()                       # the pinned buffers of this slot have been written out
+                    self.render_pose(c2w, H, W, out=frame, **pose_args)
+                    p8 = ops.frame_to8b(frame[:, 0:3].reshape(H, W, 3), frame[:, 3].reshape(H, W))
+                    for e, plane, (b, n) in zip(encs, p8, pinned[i % 2]):
+                        e.launch(plane)
+                        b.copy_(e.out, non_blocking=True)
+                        n.copy_(e.size, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    jobs.append(pool.submit(append, ev, pinned[i % 2]))
+                return [j.result() for j in jobs]
+            finally:
+                pool.shutdown()
+                for w in writers:
+                    w.close()
+
     def capture_pose(self, H, W, **kwargs):
         """One hipGraph of ``render_pose(c2w, H, W, **kwargs)``: ``PoseGraph.replay(c2w)`` writes the pose into the graph's device buffer and replays it."""
         return PoseGraph(self, H, W, **kwargs)

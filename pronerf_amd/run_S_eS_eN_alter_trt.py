@@ -387,6 +387,10 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     ``pnrf_device_png`` goes one step further: those planes stay on the device and both PNG files are encoded there (``ops.PngEncoder``; rank 0
     encodes the gathered frame under ``torchrun``), the worker thread writes the finished bytes; the files decode to the same pixels and are smaller.
     ``pnrf_lpips`` (an ``ops.Lpips``) takes LPIPS of every pose against ``gt_imgs[i]`` on the rendered rows, into ``render_kwargs['lpips']``.
+    ``pnrf_video`` = ``{'fps': 30, 'quality': 90}`` (or True for those) also writes ``<savedir>/video.avi`` (RGB) and ``video_depth.avi`` (gray, the depth
+    plane normalised per frame as in the depth PNG): Motion-JPEG, one frame per pose, each encoded on the device from ``ops.frame_to8b``'s planes
+    (``ops.JpegEncoder``; rank 0, from the gathered frame) and appended by the worker thread (``video.MjpegAviWriter``).  PNG files, returned arrays,
+    metrics and timings are as without it.
 
     ``pnrf_scene_cache`` = 'f32' | 'u8' (opt-in as well) keeps the source views on the device (``ops.Scene``, built once from ``images`` / ``poses`` /
     ``ref_K``) and renders every pose with ``Renderer.render_pose``: neighbour ranking, projection matrices, neighbour texels and rays are kernels
@@ -407,6 +411,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     dev_metrics, dev_to8b, ssims = bool(render_kwargs.get('pnrf_metrics')), bool(render_kwargs.get('pnrf_device_to8b')), []
     lpips_fn, lpips_vals = render_kwargs.get('pnrf_lpips'), []
     dev_png, png_enc = bool(render_kwargs.get('pnrf_device_png')), None
+    video, vid = render_kwargs.get('pnrf_video'), None
     from concurrent.futures import ThreadPoolExecutor
     from .dist import FrameGather, world as _world
     from .render import RayPartition
@@ -521,12 +526,25 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
                 else:
                     png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgbs1[-1])))
                     png_jobs.append(png_pool.submit(_write_png, os.path.join(savedir, 'depth_{:03d}.png'.format(i)), to8b(depths[-1] / np.max(depths[-1]))))
+                if video:            # the same planes as JPEG frames of two Motion-JPEG files (ops.JpegEncoder); the worker thread appends the finished bytes
+                    if vid is None:
+                        from .video import MjpegAviWriter
+                        vo = {'fps': 30, 'quality': 90, **(video if isinstance(video, dict) else {})}
+                        vid = (ops.JpegEncoder(H, W, 3, dev, vo['quality']), ops.JpegEncoder(H, W, 1, dev, vo['quality']),
+                               MjpegAviWriter(os.path.join(savedir, 'video.avi'), W, H, vo['fps']), MjpegAviWriter(os.path.join(savedir, 'video_depth.avi'), W, H, vo['fps'], gray=True))
+                    rgb8, depth8 = ops.frame_to8b(rgb1, depth_map)
+                    png_jobs.append(png_pool.submit(vid[2].add, vid[0].encode_to_host(rgb8)))
+                    png_jobs.append(png_pool.submit(vid[3].add, vid[1].encode_to_host(depth8)))
             walls.append((time.perf_counter() - tw) * 1e3)
         for j in png_jobs:
             j.result()                                                      # re-raises a writer's exception
         if png_pool is not None:
             png_pool.shutdown()
     finally:
+        if vid is not None:                                             # frame counts and sizes go into the headers; after a failure the files hold what was added
+            if png_pool is not None:
+                png_pool.shutdown()
+            vid[2].close(); vid[3].close()
         if rend is not None:                                            # the cached renderer outlives this call (and a failed one): the scene's texel cache does not
             rend.scene = rend._pose_ws = None
     render_kwargs['pose_wall_ms'] = walls                             # host wall time per pose: set-up, n_timing_reps renders, gather, read-back
@@ -632,6 +650,8 @@ def train(argv=None, device='cuda'):
         kw['pnrf_lpips'] = lpips_from_args(args, device)        # raises before anything is rendered when a weight file is missing
     kw['pnrf_device_to8b'] = bool(getattr(args, 'device_to8b', False))
     kw['pnrf_device_png'] = bool(getattr(args, 'device_png', False))
+    if getattr(args, 'video', False):
+        kw['pnrf_video'] = {'fps': getattr(args, 'video_fps', 30), 'quality': getattr(args, 'video_quality', 90)}
     if getattr(args, 'scene_cache', None) not in (None, 'None', 'off'):
         kw['pnrf_scene_cache'] = args.scene_cache
     if args.max_images is not None:
